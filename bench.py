@@ -7,11 +7,14 @@ bf16 compute, synthetic seeded weights and inputs.  One "step" = one batch of B 
 z_T -> 50 NFE (each = one 2B-row U-ViT forward + fused CFG/solver epilogue) -> all-gather of the final
 latents over RCCL (N > 1) -> decode of the rank's own B latents.
 
-  python bench.py [--gpus N --steps K --warmup W --batch B]
+  python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU, RCCL over xGMI)
 
 Rank 0 prints one JSON line.  `value` = images/sec of the whole job = N*B*K / max-over-ranks wall time.
-The CPU baseline (rank 0, N = 1 only, after the GPU timing) times the fp32 CPU oracle on a bounded sample of the
+A plain run sets up, warms up, times the K steps and prints the line.  `--dump-outputs DIR` also writes what the
+last timed step returned as DIR/<name>.npy (float32).  `--full` adds the measurements that take runs of their own:
+the GEMM roofline (one more eager sample of the last step's batch with HIP events around every GEMM launch) and the
+CPU baseline (rank 0, N = 1 only, after the GPU timing), which times the fp32 CPU oracle on a bounded sample of the
 same workload: one full 50-NFE CFG sample of 2 images + their decode.
 """
 import argparse
@@ -62,7 +65,14 @@ def parse():
     ap.add_argument("--no-decode", action="store_true")
     ap.add_argument("--decode-lanes", type=int, default=2, help="concurrent decode chunks (libs/autoencoder.py)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the GEMM roofline (an eager pass of its own after the timed region) and the "
+                         "CPU baseline (the fp32 oracle on the host)")
+    ap.add_argument("--cpu-baseline", choices=["auto", "off"], default="auto",
+                    help="with --full: 'off' leaves the CPU baseline out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float32; a fixed seeded "
+                         "sample of an output too large for the 64 MB budget)")
     ap.add_argument("--precision", choices=["bf16", "fp8", "fp8-all"], default=None,
                     help="override the config's block-Linear precision (configs[4] default: fp8)")
     return ap.parse_args()
@@ -157,10 +167,13 @@ def main():
         else:
             ys.append(y.to(dev) if y is not None else None)
 
-    from panopticdiffusionmodels_amd import _lib
-    prof = _lib.GemmProfiler(net.native(), max_launches=512)
+    prof = None
+    if args.full:
+        from panopticdiffusionmodels_amd import _lib
+        prof = _lib.GemmProfiler(net.native(), max_launches=512)
 
     ev = []   # (start, after sampling, after decode) HIP events per timed step, on the launch stream
+    last = {}   # what the newest step handed back, by name (--dump-outputs)
 
     def one_step(s, timed=False):
         if timed:
@@ -168,7 +181,8 @@ def main():
             e[0].record()
         if t2i:
             ids, mt = ys[s]
-            z, _pred_mask = sampler.sample(zs[s], clip.encode_tokens(ids), empty_ctx, mt)
+            z, pred_mask = sampler.sample(zs[s], clip.encode_tokens(ids), empty_ctx, mt)
+            last["pred_mask"] = pred_mask
         else:
             z = sampler.sample(zs[s], ys[s])
         if distributed:
@@ -179,6 +193,9 @@ def main():
         if timed:
             e[2].record()
             ev.append(e)
+        last["latents"] = z
+        if ae is not None:
+            last["images"] = out
         return out
 
     for s in range(args.warmup):
@@ -200,22 +217,26 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last, rank, world)
 
-    # ---- roofline of the dominant kernel (the bf16 GEMM family), after the timed region: the last step's inputs
-    # sampled once more eagerly with libpdm's HIP events around every GEMM launch (recorded on the launch stream);
-    # the last forward's launches are read back -- the kernels and shapes of the timed steps
-    prof.enable()
-    if t2i:
-        ids, mt = ys[-1]
-        T2ISampler(net, cfg_scale=full["cfg_scale"], steps=full["sample_steps"], use_graph=False).sample(
-            zs[-1], clip.encode_tokens(ids), empty_ctx, mt)
-    else:
-        sampler.sample(zs[-1], ys[-1], eager=True)
-    prof.disable()
-    torch.cuda.synchronize(dev)
-    roof = gemm_roofline(prof, ncfg, 2 * B if t2i or sampler.cfg else B, precision, config=args.config)
     samp_ms = sum(e[0].elapsed_time(e[1]) for e in ev) / len(ev)
     dec_ms = sum(e[1].elapsed_time(e[2]) for e in ev) / len(ev)
+    roof = None
+    if args.full:
+        # ---- roofline of the dominant kernel (the bf16 GEMM family), after the timed region: the last step's inputs
+        # sampled once more eagerly with libpdm's HIP events around every GEMM launch (recorded on the launch
+        # stream); the last forward's launches are read back -- the kernels and shapes of the timed steps
+        prof.enable()
+        if t2i:
+            ids, mt = ys[-1]
+            T2ISampler(net, cfg_scale=full["cfg_scale"], steps=full["sample_steps"], use_graph=False).sample(
+                zs[-1], clip.encode_tokens(ids), empty_ctx, mt)
+        else:
+            sampler.sample(zs[-1], ys[-1], eager=True)
+        prof.disable()
+        torch.cuda.synchronize(dev)
+        roof = gemm_roofline(prof, ncfg, 2 * B if t2i or sampler.cfg else B, precision, config=args.config)
     if roof and roof.get("flops_per_forward"):
         # the timed configuration itself (two concurrent lanes of half the rows, graph replay) has overlapping
         # kernels whose durations are not rates; this bounds the GEMM family's rate there from below
@@ -257,12 +278,38 @@ def main():
         "breakdown_ms_per_step": {"sample_50nfe": round(samp_ms, 2), "decode": round(dec_ms, 2),
                                   "note": "HIP events on the launch stream around each timed step (graph replay)"},
     }
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+    if not args.full:
+        del res["roofline"]   # measured by a pass of its own (--full)
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto":
         res["cpu_baseline"] = cpu_baseline(full, ncfg, ae is not None)
     if rank == 0:
         print(json.dumps(res), flush=True)
     if distributed:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET = 60 * 2 ** 20   # bytes of float32 over all dumped arrays
+
+
+def dump_outputs(out_dir, tensors, rank, world):
+    """Write the named outputs of the last timed step as <out_dir>/<name>.npy (float32; rank r > 0 of a multi-GPU
+    job writes <name>.rank<r>.npy).  The arrays share DUMP_BUDGET, smallest first, each at most an equal part of
+    what is left; one that is larger than its part is written as the values at a fixed seeded set of flat indices
+    (ascending), the same in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET // 4
+    order = sorted(tensors.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    for i, (name, t) in enumerate(order):
+        a = t.detach().to(device="cpu", dtype=torch.float32).contiguous()
+        share = left // (len(order) - i)
+        left -= min(share, a.numel())
+        if a.numel() > share:
+            g = torch.Generator().manual_seed(20240 + a.numel() % 1_000_003)
+            idx = torch.randperm(a.numel(), generator=g)[:share].sort().values
+            a = a.reshape(-1)[idx]
+        suffix = "" if rank == 0 or world == 1 else f".rank{rank}"
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), a.numpy())
 
 
 def decode_expected(full):

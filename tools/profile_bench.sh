@@ -15,7 +15,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 PARGS=""
 [ -n "$PREC" ] && PARGS="--precision $PREC"
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 bench.py --config $CONFIG --batch $BATCH --steps 2 --warmup 1 --cpu-baseline off $PARGS > $OUT/bench_kt.log 2>&1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt -o run --output-format csv -- python3 bench.py --config $CONFIG --batch $BATCH --steps 2 --warmup 1 --full --cpu-baseline off $PARGS > $OUT/bench_kt.log 2>&1
 echo "kernel trace done"; tail -1 $OUT/bench_kt.log | cut -c1-200
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE -d $OUT/fetch -o run --output-format csv -- python3 tools/time_forward.py $CONFIG $ROWS 2 ${PREC:-bf16} > $OUT/fetch.log 2>&1
 echo "fetch pass done"
