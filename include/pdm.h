@@ -295,8 +295,49 @@ int pdm_decoder_workspace_size(const pdm_decoder* d, int batch, size_t* bytes);
 int pdm_decoder_decode(pdm_decoder* d, const float* z, float* img, int batch, void* workspace,
                        size_t workspace_bytes, void* stream);
 /* GroupNorm statistics from the producing convolution / linear epilogues (default 1); 0 = a separate statistics
- * pass over every GroupNorm input (A/B and parity tests).  Process-wide; not thread-safe against a running decode. */
+ * pass over every GroupNorm input (A/B and parity tests).  Process-wide; not thread-safe against a running decode.
+ * The encoder below runs the same layers and obeys the same switch. */
 int pdm_decoder_set_gn_fusion(int on);
+
+/* ---------------------------------------------------------------------------------------------------
+ * KL-f8 encoder: FrozenAutoencoderKL.encode_moments (libs/autoencoder.py:428-431) = Encoder.forward
+ * (libs/autoencoder.py:275-300) -> quant_conv.  Weights are registered under the reference state_dict keys
+ * (encoder.*, quant_conv.*) with the decoder's repacks:
+ *   3x3 convs (ResnetBlock convs, downsample.conv, encoder.conv_out [8 rows]): bf16 [Cout][3][3][Cin]
+ *   mid.attn_1.{q,k,v}: packed into "encoder.mid.attn_1.qkv.weight" bf16 [3C][C] + ".qkv.bias" f32 [3C]
+ *   proj_out / nin_shortcut (1x1): bf16 [Cout][Cin]
+ *   encoder.conv_in [C][3][3][3], quant_conv [8][8], norms, biases: fp32 in the reference layout
+ * Downsample (pad right / bottom by one, 3x3 stride 2) runs as a gather into a bf16 [pixels][9 Cin] matrix
+ * followed by the dense GEMM.  GroupNorm fusion follows pdm_decoder_set_gn_fusion.
+ * Input img: fp32 [B, 3, S, S] (NCHW), S = latent_size * 2^(num_levels - 1) <= 512; output moments: fp32
+ * [B, 8, latent, latent] (NCHW; mean = channels 0..3, logvar = 4..7).
+ * Limits (create returns PDM_ERR_ARG otherwise): 1..4 levels, in_channels 3, z_channels 4 with double_z, every
+ * channel count a multiple of 64 and <= 1024, latent_size a multiple of 8. */
+typedef struct pdm_encoder pdm_encoder;
+
+typedef struct pdm_encoder_cfg {
+  int ch;              /* 128 */
+  int ch_mult[4];      /* (1, 2, 4, 4) */
+  int num_levels;      /* len(ch_mult) */
+  int num_res_blocks;  /* 2 */
+  int in_channels;     /* 3 */
+  int z_channels;      /* 4 */
+  int double_z;        /* 1: conv_out / quant_conv produce 2 * z_channels moments */
+  int latent_size;     /* h = w of the moments: 32 (256x256 images) or 64 (512x512) */
+} pdm_encoder_cfg;
+
+int pdm_encoder_create(const pdm_encoder_cfg* cfg, pdm_encoder** out);
+int pdm_encoder_destroy(pdm_encoder* e);
+int pdm_encoder_param_count(const pdm_encoder* e);
+int pdm_encoder_param_info(const pdm_encoder* e, int i, char* name, int len, int* dtype, long long* numel);
+int pdm_encoder_set_param(pdm_encoder* e, const char* name, const void* dev_ptr, int dtype, long long numel);
+int pdm_encoder_workspace_size(const pdm_encoder* e, int batch, size_t* bytes);
+int pdm_encoder_encode_moments(pdm_encoder* e, const float* img, float* moments, int batch, void* workspace,
+                               size_t workspace_bytes, void* stream);
+/* FrozenAutoencoderKL.sample (libs/autoencoder.py:433-439): z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20))
+ * * noise); moments fp32 [B, 2C, hw], noise and z fp32 [B, C, hw] */
+int pdm_moments_sample(const float* moments, const float* noise, float* z, int B, int C, int hw, float scale,
+                       void* stream);
 
 /* ---- output stage (utils.sample2dir, utils.py:561-640) ------------------------------------------
  * Decoded images fp32 [B, C, H, W] -> uint8 [B, H, W, C]: unpreprocess (datasets.py:104-108) followed by

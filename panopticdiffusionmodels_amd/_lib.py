@@ -34,6 +34,12 @@ class PdmDecoderCfg(ctypes.Structure):
                 ("latent_size", ctypes.c_int), ("scale_factor", ctypes.c_float)]
 
 
+class PdmEncoderCfg(ctypes.Structure):
+    _fields_ = [("ch", ctypes.c_int), ("ch_mult", ctypes.c_int * 4), ("num_levels", ctypes.c_int),
+                ("num_res_blocks", ctypes.c_int), ("in_channels", ctypes.c_int), ("z_channels", ctypes.c_int),
+                ("double_z", ctypes.c_int), ("latent_size", ctypes.c_int)]
+
+
 class PdmClipCfg(ctypes.Structure):
     _fields_ = [("vocab", ctypes.c_int), ("width", ctypes.c_int), ("layers", ctypes.c_int), ("heads", ctypes.c_int),
                 ("mlp_hidden", ctypes.c_int), ("max_position", ctypes.c_int), ("eps", ctypes.c_float)]
@@ -161,6 +167,18 @@ _SIGS = {
     "pdm_decoder_decode": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "pdm_decoder_set_gn_fusion": (ctypes.c_int, [ctypes.c_int]),
+    "pdm_encoder_create": (ctypes.c_int, [ctypes.POINTER(PdmEncoderCfg), ctypes.POINTER(ctypes.c_void_p)]),
+    "pdm_encoder_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "pdm_encoder_param_count": (ctypes.c_int, [ctypes.c_void_p]),
+    "pdm_encoder_param_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int,
+                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_longlong)]),
+    "pdm_encoder_set_param": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_longlong]),
+    "pdm_encoder_workspace_size": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_size_t)]),
+    "pdm_encoder_encode_moments": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "pdm_moments_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                          ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
     # training step (include/pdm.h "training")
     "pdm_train_create": (ctypes.c_int, [ctypes.POINTER(PdmUvitCfg), ctypes.POINTER(ctypes.c_void_p)]),
     "pdm_train_destroy": (ctypes.c_int, [ctypes.c_void_p]),

@@ -6,6 +6,11 @@
 // into the source address), with bias and the residual add fused into the epilogue (EPI_F32 accumulate
 // into the residual stream).  The mid attention block (single head over h*w tokens, C = 512) runs as a
 // packed qkv GEMM, batched Q K^T / P V GEMMs and a row softmax.
+//
+// The KL-f8 encoder (libs/autoencoder.py:209-300 + quant_conv, FrozenAutoencoderKL.encode_moments 428-431) is the
+// second half of this file: the same layers in Encoder.forward order plus the kernels of encoder.hip (conv_in, the
+// stride-2 downsample's gather in front of the dense GEMM, the conv_out + quant_conv tail, and the elementwise
+// FrozenAutoencoderKL.sample).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -410,6 +415,7 @@ struct DWork {
   double* part;   // GN partials
   float* stats;   // GN (mean, rstd) [B, 32, 2]
   bf16* zero;     // 256 zero bytes
+  bf16* A;        // encoder only: the downsample's gathered GEMM operand [B * (H/2) * (W/2), 9 C]
   size_t bytes;
 };
 
@@ -739,6 +745,205 @@ int pdm_decoder_decode(pdm_decoder* d, const float* z, float* img, int B, void* 
                          B, res, res, cin, cw, cb, img, d->cfg.out_ch);
   }
   D_HIP(hipGetLastError());
+  return PDM_OK;
+}
+
+
+}  // extern "C"
+
+// =====================================================================================================
+// KL-f8 encoder: FrozenAutoencoderKL.encode_moments (libs/autoencoder.py:428-431) = Encoder.forward (275-300) ->
+// quant_conv.  The layer set is the decoder's (resblock, attnblock, groupnorm, the implicit-GEMM conv3 and the dense
+// linear above, with the same GroupNorm-partials protocol); new are conv_in, the downsample gather and the tail.
+struct pdm_encoder {
+  pdm_encoder_cfg cfg;
+  int nlev, top_ch, side;
+  pdm_decoder tab;   // the parameter table (names, dtypes, device pointers) in the form the shared layers read
+};
+
+namespace {
+
+DWork elayout(const pdm_encoder* e, int B, char* base, size_t* a_bytes = nullptr) {
+  DWork w{};
+  size_t off = 0;
+  auto take = [&](size_t n) {
+    char* p = base ? base + off : nullptr;
+    off = aup(off + n);
+    return p;
+  };
+  // largest activation and largest gathered downsample operand over the levels
+  size_t maxe = 0, maxa = 0;
+  int res = e->side, cin = e->cfg.ch;
+  for (int lvl = 0; lvl < e->nlev; ++lvl) {
+    const int cout = e->cfg.ch * e->cfg.ch_mult[lvl];
+    maxe = std::max(maxe, (size_t)res * res * std::max(cin, cout));
+    cin = cout;
+    if (lvl != e->nlev - 1) {
+      maxa = std::max(maxa, (size_t)(res / 2) * (res / 2) * 9 * cin);
+      res /= 2;
+    }
+  }
+  const size_t hw = (size_t)res * res;
+  const int T = e->top_ch;
+  w.X = (float*)take((size_t)B * maxe * 4);
+  w.X2 = (float*)take((size_t)B * maxe * 4);
+  w.G = (bf16*)take((size_t)B * maxe * 2);
+  w.H = (bf16*)take((size_t)B * maxe * 2);
+  w.A = (bf16*)take((size_t)B * maxa * 2);
+  if (a_bytes) *a_bytes = (size_t)B * maxa * 2;
+  w.QKV = (bf16*)take((size_t)B * hw * 3 * T * 2);
+  w.S = (float*)take((size_t)B * hw * hw * 4);
+  w.P = (bf16*)take((size_t)B * hw * hw * 2);
+  w.VT = (bf16*)take((size_t)B * hw * T * 2);
+  w.O = (bf16*)take((size_t)B * hw * T * 2);
+  w.part = (double*)take((size_t)B * ((size_t)e->side * e->side / GN_PIX + 1) * 32 * 2 * sizeof(double));
+  w.stats = (float*)take((size_t)B * 32 * 2 * 4);
+  w.zero = (bf16*)take(256);
+  w.bytes = off;
+  return w;
+}
+
+// Downsample.forward (libs/autoencoder.py:65-69): X (fp32 NHWC, res x res x C) -> X2 (res/2 x res/2 x C), swapped
+int downsample(const DCtx& c, float*& X, float*& X2, int B, int res, int C, const std::string& p) {
+  const int ro = res / 2;
+  const long long M = (long long)B * ro * ro;
+  D_HIP(pdm::down_gather_launch(X, c.w->A, B, res, res, C, c.s));
+  D_TRY(linear(c, c.w->A, (int)M, 9 * C, c.d->w(p + ".weight"), c.d->f(p + ".bias"), C, pdm::EPI_F32, nullptr, X2, 0,
+               ro * ro));
+  float* t = X;
+  X = X2;
+  X2 = t;
+  return PDM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pdm_encoder_create(const pdm_encoder_cfg* cfg, pdm_encoder** out) {
+  if (!cfg || !out) return dfail(PDM_ERR_ARG, "pdm_encoder_create: null argument");
+  const pdm_encoder_cfg& c = *cfg;
+  if (c.num_levels < 1 || c.num_levels > 4) return dfail(PDM_ERR_ARG, "encoder: 1..4 levels supported");
+  if (c.in_channels != 3) return dfail(PDM_ERR_ARG, "encoder: in_channels must be 3");
+  if (c.z_channels != 4 || !c.double_z) return dfail(PDM_ERR_ARG, "encoder: z_channels must be 4 with double_z");
+  if (c.num_res_blocks < 1) return dfail(PDM_ERR_ARG, "encoder: num_res_blocks must be >= 1");
+  if (c.ch <= 0 || c.ch % 64 || c.ch > 1024)
+    return dfail(PDM_ERR_ARG, "encoder: channel counts must be multiples of 64, <= 1024");
+  for (int i = 0; i < c.num_levels; ++i)
+    if (c.ch_mult[i] <= 0 || (c.ch * c.ch_mult[i]) % 64 || c.ch * c.ch_mult[i] > 1024)
+      return dfail(PDM_ERR_ARG, "encoder: channel counts must be multiples of 64, <= 1024");
+  if (c.latent_size <= 0 || c.latent_size % 8 || (c.latent_size << (c.num_levels - 1)) > 512)
+    return dfail(PDM_ERR_ARG, "encoder: latent size must be a multiple of 8 and the image side "
+                              "latent * 2^(levels - 1) at most 512");
+  pdm_encoder* e = new pdm_encoder();
+  e->cfg = c;
+  e->nlev = c.num_levels;
+  e->top_ch = c.ch * c.ch_mult[c.num_levels - 1];
+  e->side = c.latent_size << (c.num_levels - 1);
+  pdm_decoder& d = e->tab;
+  const int T = e->top_ch;
+  d.add("encoder.conv_in.weight", PDM_F32, 27LL * c.ch);
+  d.add("encoder.conv_in.bias", PDM_F32, c.ch);
+  int cin = c.ch;
+  for (int lvl = 0; lvl < e->nlev; ++lvl) {
+    const int cout = c.ch * c.ch_mult[lvl];
+    for (int b = 0; b < c.num_res_blocks; ++b) {
+      d.add_res("encoder.down." + std::to_string(lvl) + ".block." + std::to_string(b), cin, cout);
+      cin = cout;
+    }
+    if (lvl != e->nlev - 1) {
+      d.add("encoder.down." + std::to_string(lvl) + ".downsample.conv.weight", PDM_BF16, 9LL * cin * cin);
+      d.add("encoder.down." + std::to_string(lvl) + ".downsample.conv.bias", PDM_F32, cin);
+    }
+  }
+  d.add_res("encoder.mid.block_1", T, T);
+  d.add("encoder.mid.attn_1.norm.weight", PDM_F32, T);
+  d.add("encoder.mid.attn_1.norm.bias", PDM_F32, T);
+  d.add("encoder.mid.attn_1.qkv.weight", PDM_BF16, 3LL * T * T);
+  d.add("encoder.mid.attn_1.qkv.bias", PDM_F32, 3LL * T);
+  d.add("encoder.mid.attn_1.proj_out.weight", PDM_BF16, 1LL * T * T);
+  d.add("encoder.mid.attn_1.proj_out.bias", PDM_F32, T);
+  d.add_res("encoder.mid.block_2", T, T);
+  d.add("encoder.norm_out.weight", PDM_F32, T);
+  d.add("encoder.norm_out.bias", PDM_F32, T);
+  d.add("encoder.conv_out.weight", PDM_BF16, 8LL * 9 * T);
+  d.add("encoder.conv_out.bias", PDM_F32, 8);
+  d.add("quant_conv.weight", PDM_F32, 64);
+  d.add("quant_conv.bias", PDM_F32, 8);
+  *out = e;
+  return PDM_OK;
+}
+
+int pdm_encoder_destroy(pdm_encoder* e) {
+  delete e;
+  return PDM_OK;
+}
+
+int pdm_encoder_param_count(const pdm_encoder* e) { return e ? pdm_decoder_param_count(&e->tab) : 0; }
+
+int pdm_encoder_param_info(const pdm_encoder* e, int i, char* name, int len, int* dtype, long long* numel) {
+  if (!e) return dfail(PDM_ERR_ARG, "pdm_encoder_param_info: null handle");
+  return pdm_decoder_param_info(&e->tab, i, name, len, dtype, numel);
+}
+
+int pdm_encoder_set_param(pdm_encoder* e, const char* name, const void* ptr, int dtype, long long numel) {
+  if (!e) return dfail(PDM_ERR_ARG, "pdm_encoder_set_param: null handle");
+  return pdm_decoder_set_param(&e->tab, name, ptr, dtype, numel);
+}
+
+int pdm_encoder_workspace_size(const pdm_encoder* e, int B, size_t* bytes) {
+  if (!e || B <= 0 || !bytes) return dfail(PDM_ERR_ARG, "pdm_encoder_workspace_size: bad argument");
+  *bytes = elayout(e, B, nullptr).bytes;
+  return PDM_OK;
+}
+
+int pdm_encoder_encode_moments(pdm_encoder* e, const float* img, float* moments, int B, void* workspace,
+                               size_t workspace_bytes, void* stream) {
+  if (!e || !img || !moments || B <= 0) return dfail(PDM_ERR_ARG, "pdm_encoder_encode_moments: bad argument");
+  const pdm_decoder* d = &e->tab;
+  for (auto& n : d->order)
+    if (!d->params.at(n).ptr) return dfail(PDM_ERR_STATE, "pdm_encoder: weight not registered: " + n);
+  size_t a_bytes = 0;
+  DWork w = elayout(e, B, (char*)workspace, &a_bytes);
+  // the GEMM addresses the gathered downsample operand with 32-bit buffer offsets
+  if (a_bytes >= ((size_t)1 << 31))
+    return dfail(PDM_ERR_ARG, "pdm_encoder_encode_moments: batch too large for one launch, encode in chunks");
+  if (w.bytes > workspace_bytes) return dfail(PDM_ERR_ARG, "pdm_encoder_encode_moments: workspace too small");
+  hipStream_t s = (hipStream_t)stream;
+  bool gn_ready = false;
+  DCtx c{d, s, &w, &gn_ready};
+  D_HIP(hipMemsetAsync(w.zero, 0, 256, s));
+  const int T = e->top_ch;
+  int res = e->side, cin = e->cfg.ch;
+  float* X = w.X;
+  float* X2 = w.X2;
+  D_HIP(pdm::enc_conv_in_launch(img, d->f("encoder.conv_in.weight"), d->f("encoder.conv_in.bias"), X, B, res, res, cin, s));
+  for (int lvl = 0; lvl < e->nlev; ++lvl) {
+    const int cout = e->cfg.ch * e->cfg.ch_mult[lvl];
+    const std::string p = "encoder.down." + std::to_string(lvl);
+    for (int b = 0; b < e->cfg.num_res_blocks; ++b) {
+      D_TRY(resblock(c, X, X2, B, res, cin, cout, p + ".block." + std::to_string(b)));
+      cin = cout;
+    }
+    if (lvl != e->nlev - 1) {
+      D_TRY(downsample(c, X, X2, B, res, cin, p + ".downsample.conv"));
+      res /= 2;
+    }
+  }
+  D_TRY(resblock(c, X, X2, B, res, T, T, "encoder.mid.block_1"));
+  D_TRY(attnblock(c, X, B, res, T, "encoder.mid.attn_1"));
+  D_TRY(resblock(c, X, X2, B, res, T, T, "encoder.mid.block_2"));
+  D_TRY(groupnorm<float>(c, X, B, res * res, T, "encoder.norm_out", w.G, true));
+  D_HIP(pdm::enc_tail_launch(w.G, B, res, res, T, d->w("encoder.conv_out.weight"), d->f("encoder.conv_out.bias"),
+                             d->f("quant_conv.weight"), d->f("quant_conv.bias"), moments, s));
+  return PDM_OK;
+}
+
+int pdm_moments_sample(const float* moments, const float* noise, float* z, int B, int C, int hw, float scale,
+                       void* stream) {
+  if (!moments || !noise || !z || B <= 0 || C <= 0 || hw <= 0)
+    return dfail(PDM_ERR_ARG, "pdm_moments_sample: bad argument");
+  D_HIP(pdm::moments_sample_launch(moments, noise, z, B, C, hw, scale, (hipStream_t)stream));
   return PDM_OK;
 }
 

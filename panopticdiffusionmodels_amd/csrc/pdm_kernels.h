@@ -234,4 +234,18 @@ hipError_t rowcopy_launch(float* dst, int ldd, const float* src, int lds, int ro
                           int dst_group_stride, int src_group_stride, hipStream_t stream, float* dst2 = nullptr,
                           int ldd2 = 0, const float* src2 = nullptr, int lds2 = 0, int D2 = 0);
 
+// KL-f8 encoder kernels (encoder.hip; orchestrated by pdm_encoder_* in decoder.hip)
+// conv_in 3 -> C (3x3, pad 1): img fp32 NCHW [B, 3, H, W] (W <= 512), w fp32 [C][3][3][3] -> out fp32 NHWC
+hipError_t enc_conv_in_launch(const float* img, const float* w, const float* bias, float* out, int B, int H, int W,
+                              int C, hipStream_t s);
+// stride-2 downsample operand: x fp32 NHWC [B, H, W, C] -> A bf16 [B * (H/2) * (W/2)][9 C], columns (ky, kx, ci),
+// source pixel (2y + ky, 2x + kx), zeros at row H / column W
+hipError_t down_gather_launch(const float* x, bf16* A, int B, int H, int W, int C, hipStream_t s);
+// conv_out (C -> 8, 3x3, w bf16 [8][3][3][C]) + quant_conv (8 -> 8, fp32): g bf16 NHWC -> moments fp32 NCHW [B, 8, H, W]
+hipError_t enc_tail_launch(const bf16* g, int B, int H, int W, int C, const bf16* w, const float* cbias, const float* qw,
+                           const float* qb, float* moments, hipStream_t s);
+// z = scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * noise): moments fp32 [B, 2C, hw], noise / z fp32 [B, C, hw]
+hipError_t moments_sample_launch(const float* moments, const float* noise, float* z, int B, int C, int hw, float scale,
+                                 hipStream_t s);
+
 }  // namespace pdm

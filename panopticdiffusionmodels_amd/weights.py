@@ -6,6 +6,7 @@ from this generator.  Key names / shapes follow the probe listing in SURVEY.md Â
   * U-ViT          libs/uvit.py:138-195        (PatchEmbed 123-135, Block 95-120, Mlp libs/timm.py:96-112)
   * U-ViT t2i      libs/uvit_t2i.py:258-359    (zeroconv 246-257, mask stream 307-326, mask head 335-348)
   * KL-f8 decoder  libs/autoencoder.py:303-409 (+ post_quant_conv 420, get_model ddconfig 471-484)
+  * KL-f8 encoder  libs/autoencoder.py:209-300 (+ quant_conv 419)
 
 `init="reference"` mimics the reference init (libs/uvit.py:185-195: trunc_normal(.02) Linear
 weights and pos_embed, zero biases, LayerNorm 1/0, default Conv init, zero zeroconv); `init="random"`
@@ -151,6 +152,38 @@ def decoder_spec(ch=128, out_ch=3, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_cha
     return s
 
 
+ENCODER_DDCONFIG = dict(DECODER_DDCONFIG)   # one ddconfig builds both halves (libs/autoencoder.py:471-484)
+
+
+def encoder_spec(ch=128, ch_mult=(1, 2, 4, 4), num_res_blocks=2, z_channels=4, embed_dim=4, in_channels=3,
+                 double_z=True, prefix="encoder", **_ignored):
+    """Parameters used by FrozenAutoencoderKL.encode_moments (libs/autoencoder.py:428-431): Encoder (209-300) +
+    quant_conv (419), in the reference's state_dict order."""
+    n = len(ch_mult)
+    zc = 2 * z_channels if double_z else z_channels
+    s = [(f"{prefix}.conv_in.weight", (ch, in_channels, 3, 3), "conv_w"), (f"{prefix}.conv_in.bias", (ch,), "conv_b")]
+    block_in = ch
+    for i_level in range(n):
+        block_out = ch * ch_mult[i_level]
+        for i_block in range(num_res_blocks):
+            s += _resblock_spec(f"{prefix}.down.{i_level}.block.{i_block}", block_in, block_out)
+            block_in = block_out
+        if i_level != n - 1:
+            s += [(f"{prefix}.down.{i_level}.downsample.conv.weight", (block_in, block_in, 3, 3), "conv_w"),
+                  (f"{prefix}.down.{i_level}.downsample.conv.bias", (block_in,), "conv_b")]
+    s += _resblock_spec(f"{prefix}.mid.block_1", block_in, block_in)
+    s += [(f"{prefix}.mid.attn_1.norm.weight", (block_in,), "gn_w"), (f"{prefix}.mid.attn_1.norm.bias", (block_in,), "gn_b")]
+    for nm in ("q", "k", "v", "proj_out"):
+        s += [(f"{prefix}.mid.attn_1.{nm}.weight", (block_in, block_in, 1, 1), "conv_w"),
+              (f"{prefix}.mid.attn_1.{nm}.bias", (block_in,), "conv_b")]
+    s += _resblock_spec(f"{prefix}.mid.block_2", block_in, block_in)
+    s += [(f"{prefix}.norm_out.weight", (block_in,), "gn_w"), (f"{prefix}.norm_out.bias", (block_in,), "gn_b"),
+          (f"{prefix}.conv_out.weight", (zc, block_in, 3, 3), "conv_w"), (f"{prefix}.conv_out.bias", (zc,), "conv_b"),
+          ("quant_conv.weight", (2 * embed_dim, 2 * z_channels, 1, 1), "conv_w"),
+          ("quant_conv.bias", (2 * embed_dim,), "conv_b")]
+    return s
+
+
 def _fan_in(shape):
     f = 1
     for d in shape[1:]:
@@ -220,6 +253,13 @@ def nnet_state_dict(nnet_cfg, seed=0, init="reference", device="cpu"):
 def decoder_state_dict(seed=0, init="reference", device="cpu", ch=128, ch_mult=(1, 2, 4, 4),
                        num_res_blocks=2):
     return make_state_dict(decoder_spec(ch=ch, ch_mult=ch_mult, num_res_blocks=num_res_blocks),
+                           seed=seed, init=init, device=device)
+
+
+def encoder_state_dict(seed=0, init="reference", device="cpu", ch=128, ch_mult=(1, 2, 4, 4),
+                       num_res_blocks=2):
+    """Encoder + quant_conv weights from their own generator (the decoder's seeded weights do not depend on them)."""
+    return make_state_dict(encoder_spec(ch=ch, ch_mult=ch_mult, num_res_blocks=num_res_blocks),
                            seed=seed, init=init, device=device)
 
 
