@@ -171,6 +171,42 @@ int pdm_stage_epilogue(const pdm_stage_epilogue_args* a, void* stream);
 /* out = sum_i c[i] * T[i], n fp32 elements (generic DPM_Solver update path, dpm_solver_pytorch.py:301-432) */
 int pdm_lincomb(float* out, int n_terms, const float* const* T, const float* c, long long n, void* stream);
 
+/* ---- Euler-Maruyama step (sde.py:243-267: euler_maruyama on ReverseSDE / ODE) with on-device noise --------
+ * One step over [B, C, H, W] fp32 whose coefficients come from device memory, so one captured launch sequence
+ * (forward + this) serves every step of a trajectory.  With k = *counter (0 <= k < steps; otherwise nothing is
+ * written) and (t_net, a, b, c) = table[k]:
+ *   e = conv(pre[b]) (conv skipped if conv_w == NULL);  if has_uncond: e += cfg_scale * (e - conv(pre[b + B]))
+ *   x = a * x + b * e + c * z      written to x and to xin[0:B] (and xin[B:2B] if has_uncond)
+ *   z = the Philox normals of (seed, sample_offset + b, step k) below; not generated when c == 0
+ * and then, in a one-block launch behind it on the same stream (the counter's only writer, so every block of the
+ * step reads the same k): t_next[0:rows] = table[k + 1].t_net (if k + 1 < steps), *counter = k + 1;
+ * rows = 2B if has_uncond else B.  table: fp32 [steps, 4] rows (t_net, a, b, c) (solver_core.em_plan). */
+typedef struct pdm_em_step_args {
+  const float* pre;                      /* [B or 2B, C, H, W] net output before the final conv */
+  const float* conv_w; const float* conv_b;
+  int B, C, H, W;
+  int has_uncond; float cfg_scale;
+  float* x;                              /* [B, C, H, W] solver state, updated in place */
+  float* xin;                            /* [rows, C, H, W] batched model input (may alias x when rows == B) */
+  const float* table; int steps;
+  int* counter;                          /* device int32 step index */
+  float* t_next;                         /* [rows] net time input of the next forward */
+  unsigned long long seed;
+  unsigned long long sample_offset;      /* global index of sample 0 of this batch ... */
+  const unsigned long long* sample_offset_dev;   /* ... plus *sample_offset_dev when not NULL (device memory, read
+                                                    by the kernel: a captured step serves any batch position) */
+} pdm_em_step_args;
+int pdm_em_step(const pdm_em_step_args* a, void* stream);
+/* The noise pdm_em_step uses at step `step` for samples sample_offset .. sample_offset + B - 1: out fp32
+ * [B, per_sample].  Philox4x32-10 with key = (seed low, seed high) and counter = (quad index within the sample,
+ * step, global sample index low, high); element o takes output word o & 3 of quad o >> 2; u = ((r >> 8) + 0.5) *
+ * 2^-24; Box-Muller on the word pairs (0, 1), (2, 3): n_a = sqrt(-2 ln u_a) cos(2 pi u_b), n_b = .. sin(2 pi u_b).
+ * pdm_philox_raw writes the words r themselves (uint32 [B, per_sample]). */
+int pdm_philox_normal(float* out, int B, int per_sample, unsigned long long seed, unsigned long long sample_offset,
+                      int step, void* stream);
+int pdm_philox_raw(uint32_t* out, int B, int per_sample, unsigned long long seed, unsigned long long sample_offset,
+                   int step, void* stream);
+
 /* ---- individual kernels (exposed for parity tests and the generic Python path) -------------------- */
 /* nn.Linear on bf16 rows: libs/uvit.py:61-63,117; libs/timm.py:101-104.  W [N][K] bf16. */
 int pdm_gemm_bf16(const void* A1, int lda1, const void* A2, int lda2, int K1, const void* W, const float* bias,

@@ -57,6 +57,18 @@ class PdmStageEpilogueArgs(ctypes.Structure):
     ]
 
 
+class PdmEmStepArgs(ctypes.Structure):
+    _fields_ = [
+        ("pre", ctypes.c_void_p), ("conv_w", ctypes.c_void_p), ("conv_b", ctypes.c_void_p),
+        ("B", ctypes.c_int), ("C", ctypes.c_int), ("H", ctypes.c_int), ("W", ctypes.c_int),
+        ("has_uncond", ctypes.c_int), ("cfg_scale", ctypes.c_float),
+        ("x", ctypes.c_void_p), ("xin", ctypes.c_void_p),
+        ("table", ctypes.c_void_p), ("steps", ctypes.c_int),
+        ("counter", ctypes.c_void_p), ("t_next", ctypes.c_void_p),
+        ("seed", ctypes.c_ulonglong), ("sample_offset", ctypes.c_ulonglong), ("sample_offset_dev", ctypes.c_void_p),
+    ]
+
+
 class PdmGemmArgs(ctypes.Structure):
     _fields_ = [
         ("A1", ctypes.c_void_p), ("lda1", ctypes.c_int), ("A2", ctypes.c_void_p), ("lda2", ctypes.c_int),
@@ -111,6 +123,11 @@ _SIGS = {
     "pdm_stage_epilogue": (ctypes.c_int, [ctypes.POINTER(PdmStageEpilogueArgs), ctypes.c_void_p]),
     "pdm_lincomb": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
                                    ctypes.POINTER(ctypes.c_float), ctypes.c_longlong, ctypes.c_void_p]),
+    "pdm_em_step": (ctypes.c_int, [ctypes.POINTER(PdmEmStepArgs), ctypes.c_void_p]),
+    "pdm_philox_normal": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong,
+                                         ctypes.c_ulonglong, ctypes.c_int, ctypes.c_void_p]),
+    "pdm_philox_raw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_ulonglong,
+                                      ctypes.c_ulonglong, ctypes.c_int, ctypes.c_void_p]),
     "pdm_gemm_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
@@ -554,6 +571,70 @@ def stage_epilogue(pre, B, conv_w=None, conv_b=None, cfg_scale=None, act_tanh=Fa
     a.x_out2 = x_out2.data_ptr() if x_out2 is not None else None
     a.x_out3 = x_out3.data_ptr() if x_out3 is not None else None
     check(lib.pdm_stage_epilogue(ctypes.byref(a), stream_ptr(pre.device)), "pdm_stage_epilogue")
+
+
+def em_step_args(pre, B, x, xin, table, counter, t_next, conv_w=None, conv_b=None, cfg_scale=None, seed=0,
+                 sample_offset=0, sample_offset_dev=None):
+    """The pdm_em_step_args of one Euler-Maruyama step (include/pdm.h); host-side checks only, no GPU call.
+    sample_offset_dev: an int64 device tensor whose first element is added to sample_offset by the kernel."""
+    if pre.dim() != 4:
+        raise ValueError("em_step: pre must be [B or 2B, C, H, W]")
+    rows = 2 * B if cfg_scale is not None else B
+    _, C, H, W = pre.shape
+    if B <= 0 or pre.shape[0] != rows or tuple(x.shape) != (B, C, H, W) or tuple(xin.shape) != (rows, C, H, W):
+        raise ValueError(f"em_step: pre / xin must hold {rows} rows and x {B} rows of one [C, H, W] shape")
+    if table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1 or table.dtype != torch.float32:
+        raise ValueError("em_step: table must be fp32 [steps, 4] with steps >= 1")
+    if counter.dtype != torch.int32 or counter.numel() < 1:
+        raise ValueError("em_step: counter must be an int32 tensor")
+    if t_next.dtype != torch.float32 or t_next.numel() != rows:
+        raise ValueError(f"em_step: t_next must be fp32 [{rows}]")
+    for t in (pre, x, xin, table):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("em_step: tensors must be contiguous fp32")
+    if (conv_w is None) != (conv_b is None):
+        raise ValueError("em_step: conv weight and bias go together")
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(sample_offset) < 2 ** 64:
+        raise ValueError("em_step: seed and sample_offset must fit 64 bits")
+    a = PdmEmStepArgs()
+    a.pre = pre.data_ptr()
+    a.conv_w = conv_w.data_ptr() if conv_w is not None else None
+    a.conv_b = conv_b.data_ptr() if conv_b is not None else None
+    a.B, a.C, a.H, a.W = B, C, H, W
+    a.has_uncond = int(cfg_scale is not None)
+    a.cfg_scale = float(cfg_scale or 0.0)
+    a.x, a.xin = x.data_ptr(), xin.data_ptr()
+    a.table, a.steps = table.data_ptr(), table.shape[0]
+    a.counter, a.t_next = counter.data_ptr(), t_next.data_ptr()
+    a.seed, a.sample_offset = int(seed), int(sample_offset)
+    if sample_offset_dev is not None:
+        if sample_offset_dev.dtype != torch.int64 or sample_offset_dev.numel() < 1:
+            raise ValueError("em_step: sample_offset_dev must be an int64 tensor")
+        a.sample_offset_dev = sample_offset_dev.data_ptr()
+    return a
+
+
+def em_step(pre, B, x, xin, table, counter, t_next, **kw):
+    """One Euler-Maruyama step on the GPU (pdm_em_step): x, xin, t_next and counter are updated in place."""
+    a = em_step_args(pre, B, x, xin, table, counter, t_next, **kw)
+    require_gpu(pre)
+    check(load().pdm_em_step(ctypes.byref(a), stream_ptr(pre.device)), "pdm_em_step")
+
+
+def philox_normal(B, per_sample, seed=0, sample_offset=0, step=0, device="cuda", raw=False):
+    """The noise pdm_em_step draws at `step` for samples sample_offset .. + B - 1 (pdm_philox_normal): fp32
+    [B, per_sample]; raw=True returns the Philox words instead (pdm_philox_raw: int32 holding the uint32 bits)."""
+    if B <= 0 or per_sample <= 0 or step < 0:
+        raise ValueError("philox_normal: B, per_sample must be positive and step >= 0")
+    if not 0 <= int(seed) < 2 ** 64 or not 0 <= int(sample_offset) < 2 ** 64:
+        raise ValueError("philox_normal: seed and sample_offset must fit 64 bits")
+    require_gpu()
+    dev = torch.device(device)
+    out = torch.empty(B, per_sample, dtype=torch.int32 if raw else torch.float32, device=dev)
+    fn = load().pdm_philox_raw if raw else load().pdm_philox_normal
+    check(fn(ptr(out), B, per_sample, int(seed), int(sample_offset), int(step), stream_ptr(dev)),
+          "pdm_philox_raw" if raw else "pdm_philox_normal")
+    return out
 
 
 def wgrad(dy, x, out=None, accumulate=False, scratch_mb=64):

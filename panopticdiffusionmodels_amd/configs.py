@@ -122,6 +122,15 @@ CONFIGS = {
 }
 
 
+# What the reference's own config file selects for sampling (config.sample.algorithm / sample_steps; eval.py:65-71,
+# eval_ldm.py:89-93): the pixel-space CIFAR config samples with sde.euler_maruyama on the ReverseSDE, 1000 steps
+# (configs/cifar10_uvit_small.py:55-61; sampler.EulerMaruyamaSampler), every other one with DPM-Solver, 50 steps.
+# Informational: `front_end` / `sample_steps` above stay what bench.py and the fused DPM-Solver samplers run.
+for _name, _cfg in CONFIGS.items():
+    _cfg["reference_sample"] = (dict(algorithm="euler_maruyama_sde", sample_steps=1000)
+                                if _name == "cifar10_uvit_small" else dict(algorithm="dpm_solver", sample_steps=50))
+
+
 def get_config(name):
     if name not in CONFIGS:
         raise KeyError(f"unknown config {name!r}; known: {sorted(CONFIGS)}")

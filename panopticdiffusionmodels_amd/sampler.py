@@ -10,6 +10,10 @@ each a separate PyTorch launch, plus host syncs inside the discrete schedule.  H
 
 with every coefficient precomputed on the host (solver_core).  Nothing in the loop synchronises with the
 host, so the 50-NFE loop for a fixed batch is captured once into a HIP graph and replayed.
+
+The Euler-Maruyama SDE / ODE loop (sde.py:243-267; EulerMaruyamaSampler) runs up to 1000 steps and needs fresh noise
+in each, so its step reads the coefficients from device memory and draws the noise in the kernel (pdm_em_step):
+a short block of identical steps is captured and replayed instead of the whole trajectory.
 """
 
 import torch
@@ -200,6 +204,148 @@ class ClassCondSampler:
                 self._loop(st, B)
             st["graph"] = g
         st["graph"].replay()
+        return st["x"].clone()
+
+
+# Steps per captured graph of EulerMaruyamaSampler (the measured sweep is in DESIGN §5e)
+EM_CAPTURE_BLOCK = 10
+
+
+class EulerMaruyamaSampler:
+    """z_T -> z_0 with sde.euler_maruyama on ReverseSDE (kind='sde') or ODE (kind='ode') of the linear VP-SDE
+    (sde.py:202-267; eval.py:65-71, train.py:170), for a noise-prediction UViT, fully on the GPU.
+
+    One step is pdm_uvit_forward on the [cond | uncond] batch + pdm_em_step, which reads its coefficients from a
+    device table indexed by a device-resident step counter and draws its noise from Philox keyed on the global
+    sample index (philox.py).  Nothing in a step depends on which step it is, so `capture_block` consecutive steps
+    are captured once into a HIP graph and replayed steps // capture_block times (a remainder runs uncaptured).
+    The noise of sample i at step k depends only on (seed, sample_offset + i, k): not on the batch, the lanes or
+    the capture block.
+    """
+
+    def __init__(self, nnet, kind="sde", steps=1000, eps=1e-3, cfg_scale=0.0, null_label=None, seed=0,
+                 use_graph=True, lanes=1, capture_block=None):
+        self.nnet = nnet
+        self.kind, self.steps = kind, int(steps)
+        self.plan = sc.em_plan(sc.HostLinear(0.1, 20.0), self.steps, eps, 1.0, kind)
+        self.cfg = cfg_scale is not None and cfg_scale > 0
+        self.cfg_scale = float(cfg_scale or 0.0)
+        if self.cfg and nnet.num_classes <= 0:
+            raise ValueError("classifier-free guidance needs a class-conditional net")
+        # eval_ldm.py:66-74: the uncond label is the dataset's K, the last row of the label embedding
+        self.null_label = nnet.num_classes - 1 if null_label is None else null_label
+        if not 0 <= int(seed) < 2 ** 64:
+            raise ValueError("seed must fit 64 bits")
+        self.seed = int(seed)
+        self.use_graph = use_graph
+        self.lanes = max(1, int(lanes))   # concurrent sub-batches (ClassCondSampler)
+        self.capture_block = max(1, min(self.steps, int(capture_block or EM_CAPTURE_BLOCK)))
+        self._state = {}
+
+    def _buffers(self, B, device, lane=None):
+        key = (B, device, lane)
+        if key in self._state:
+            return self._state[key]
+        n = self.nnet
+        rows = 2 * B if self.cfg else B
+        shp = (n.in_chans, n.img_size, n.img_size)
+        st = dict(
+            ws=None if lane is None else torch.empty(n.native().workspace_bytes(rows), dtype=torch.uint8,
+                                                     device=device),
+            rows=rows, generation=n.generation,
+            xin=torch.empty(rows, *shp, device=device),           # batched model input [cond | uncond]
+            pre=torch.empty(rows, *shp, device=device),           # model output before the final conv
+            x=torch.empty(B, *shp, device=device),                # solver state
+            y=torch.empty(rows, dtype=torch.int64, device=device) if n.num_classes > 0 else None,
+            t=torch.empty(rows, device=device),                   # net time input of the next forward
+            table=torch.tensor(self.plan, dtype=torch.float32, device=device),
+            counter=torch.zeros(1, dtype=torch.int32, device=device),   # step index (pdm_em_step advances it)
+            offset=torch.zeros(1, dtype=torch.int64, device=device),    # global index of this batch's sample 0
+            graph=None,
+        )
+        self._state[key] = st
+        return st
+
+    def _run(self, st, B, nsteps):
+        n = self.nnet
+        w, b = n.final_conv_params()
+        for _ in range(nsteps):
+            n.forward_pre(st["xin"], st["t"], st["y"], out=st["pre"], workspace=st["ws"])
+            _lib.em_step(st["pre"], B, st["x"], st["xin"], st["table"], st["counter"], st["t"], conv_w=w, conv_b=b,
+                         cfg_scale=self.cfg_scale if self.cfg else None, seed=self.seed,
+                         sample_offset_dev=st["offset"])
+
+    def noise(self, step, B, sample_offset=0):
+        """The normals step `step` (0 = the first, t = T) adds to samples sample_offset .. sample_offset + B - 1,
+        before the step's coefficient c: [B, C, H, W] fp32 on the net's device (pdm_philox_normal)."""
+        n = self.nnet
+        dev = next(n.parameters()).device
+        shp = (n.in_chans, n.img_size, n.img_size)
+        z = _lib.philox_normal(B, shp[0] * shp[1] * shp[2], self.seed, sample_offset, step, device=dev)
+        return z.view(B, *shp)
+
+    @torch.no_grad()
+    def sample(self, z, y=None, sample_offset=0, eager=False):
+        """z [B, C, H, W] fp32 on the GPU; y [B] int64 labels (num_classes > 0); sample_offset: the global index of
+        z[0] (a sample's noise is keyed on it, so sharding a run over batches, lanes or ranks does not change any
+        sample).  Returns z_0 [B, C, H, W].  eager=True runs this call without the HIP graph."""
+        _lib.require_gpu(z)
+        if not 0 <= int(sample_offset) < 2 ** 64:
+            raise ValueError("sample_offset must fit 64 bits")
+        B = z.shape[0]
+        if not (self.lanes > 1 and B >= self.lanes and self.use_graph and not eager):
+            return self._sample_one(z, y, eager, int(sample_offset))
+        main = torch.cuda.current_stream(z.device)
+        streams = _lane_streams(self, main)
+        _fork(main, streams)   # before lane 0's work is queued on main
+        bounds = [round(i * B / self.lanes) for i in range(self.lanes + 1)]
+        outs = []
+        for i, s in enumerate(streams):
+            with torch.cuda.stream(s):
+                zi = z[bounds[i]:bounds[i + 1]]
+                yi = y[bounds[i]:bounds[i + 1]] if y is not None else None
+                outs.append(self._sample_one(zi, yi, False, int(sample_offset) + bounds[i], lane=i))
+        _join(main, streams, outs)
+        return torch.cat(outs)
+
+    def _sample_one(self, z, y, eager, offset, lane=None):
+        B = z.shape[0]
+        st = self._buffers(B, z.device, lane)
+        if st["y"] is not None:
+            if y is None:
+                raise ValueError("labels required for a class-conditional net")
+            st["y"][:B].copy_(y)
+            if self.cfg:
+                st["y"][B:].fill_(self.null_label)
+        offset &= 2 ** 64 - 1
+
+        def load():   # the trajectory's start: state, first net time, step counter, sample index
+            st["x"].copy_(z)
+            st["xin"][:B].copy_(z)
+            if self.cfg:
+                st["xin"][B:].copy_(z)
+            st["t"].copy_(st["table"][0, 0].expand(st["rows"]))
+            st["counter"].zero_()
+            st["offset"].fill_(offset - 2 ** 64 if offset >= 2 ** 63 else offset)
+        if not self.use_graph or eager:
+            load()
+            self._run(st, B, self.steps)
+            return st["x"].clone()
+        _drop_stale_graph(st, self.nnet)
+        S = self.capture_block
+        if st["graph"] is None:
+            # warm-up outside capture: builds the native handle, workspace and conv params
+            load()
+            self._run(st, B, 1)
+            torch.cuda.synchronize(z.device)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self._run(st, B, S)
+            st["graph"] = g
+        load()
+        for _ in range(self.steps // S):
+            st["graph"].replay()
+        self._run(st, B, self.steps % S)
         return st["x"].clone()
 
 

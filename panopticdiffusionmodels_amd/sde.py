@@ -1,11 +1,20 @@
-"""VP-SDE bookkeeping and ScoreModel — the hot-path subset of sde.py (VPSDE 72-113, ScoreModel 155-199).
+"""VP-SDE bookkeeping, ScoreModel and the Euler-Maruyama sampler of sde.py (VPSDE 72-113, ScoreModel 155-199,
+ReverseSDE / ODE 202-236, euler_maruyama 243-267).
 
 `ScoreModel.predict` feeds the net `t * 999` (sde.py:174); `noise_pred` is what eval_ldm.py / eval.py hand
-to dpm_solver_pytorch.model_wrapper.  The Euler-Maruyama sampler and LSimple (training) are outside the
-sampling hot path.
+to dpm_solver_pytorch.model_wrapper.  `euler_maruyama` here is the reference's loop in plain torch ops: it takes
+any callable net, runs on the CPU or the GPU and draws its noise with torch.randn_like in the reference's order.
+The fused GPU loop for a U-ViT (one captured step, noise generated on the device) is
+sampler.EulerMaruyamaSampler; LSimple (training) is train.py.
 """
 import numpy as np
 import torch
+
+try:
+    from tqdm import tqdm
+except ImportError:   # progress bar only (verbose=True); not a dependency
+    def tqdm(it, **_kw):
+        return it
 
 
 def stp(s, ts):
@@ -99,3 +108,62 @@ class ScoreModel:
 
     def score(self, xt, t, **kwargs):
         return stp(-self.sde.cum_beta(t).rsqrt(), self.noise_pred(xt, t, **kwargs))
+
+
+class ReverseSDE:
+    r"""dx = [f(x, t) - g(t)^2 s(x, t)] dt + g(t) dw   (sde.py:202-217)"""
+
+    def __init__(self, score_model):
+        self.sde = score_model.sde  # the forward sde
+        self.score_model = score_model
+
+    def drift(self, x, t, **kwargs):
+        drift = self.sde.drift(x, t)  # f(x, t)
+        diffusion = self.sde.diffusion(t)  # g(t)
+        score = self.score_model.score(x, t, **kwargs)
+        return drift - stp(diffusion ** 2, score)
+
+    def diffusion(self, t):
+        return self.sde.diffusion(t)
+
+
+class ODE:
+    r"""dx = [f(x, t) - 0.5 g(t)^2 s(x, t)] dt   (sde.py:220-236)"""
+
+    def __init__(self, score_model):
+        self.sde = score_model.sde  # the forward sde
+        self.score_model = score_model
+
+    def drift(self, x, t, **kwargs):
+        drift = self.sde.drift(x, t)  # f(x, t)
+        diffusion = self.sde.diffusion(t)  # g(t)
+        score = self.score_model.score(x, t, **kwargs)
+        return drift - 0.5 * stp(diffusion ** 2, score)
+
+    def diffusion(self, t):
+        return 0
+
+
+@torch.no_grad()
+def euler_maruyama(rsde, x_init, sample_steps, eps=1e-3, T=1, trace=None, verbose=False, **kwargs):
+    r"""The Euler-Maruyama sampler for the reverse SDE / ODE (sde.py:243-267): the grid is
+    [0, linspace(eps, T, sample_steps)] walked backwards, the last step (s == 0) adds no noise, **kwargs go to the
+    net.  torch.randn_like is called once per step with s != 0, for the ODE too (its sigma is 0), exactly where the
+    reference calls it, so the same torch seed draws the same noise."""
+    assert isinstance(rsde, ReverseSDE) or isinstance(rsde, ODE)
+    timesteps = np.append(0., np.linspace(eps, T, sample_steps))
+    timesteps = torch.tensor(timesteps).to(x_init)
+    x = x_init
+    if trace is not None:
+        trace.append(x)
+    pairs = list(zip(timesteps, timesteps[1:]))[::-1]
+    for s, t in (tqdm(pairs, desc='euler_maruyama') if verbose else pairs):
+        drift = rsde.drift(x, t, **kwargs)
+        diffusion = rsde.diffusion(t)
+        dt = s - t
+        mean = x + drift * dt
+        sigma = diffusion * (-dt).sqrt()
+        x = mean + stp(sigma, torch.randn_like(x)) if s != 0 else mean
+        if trace is not None:
+            trace.append(x)
+    return x

@@ -342,3 +342,44 @@ def pt_plan(hs, steps, t_0, t_T, order=3, skip_type="logSNR"):
 
 def nfe(plan):
     return sum(len(st) for st in plan)
+
+
+# ------------------------------------------------------------------------------------------------
+# Euler-Maruyama (sde.py:243-267)
+
+def em_grid(steps, eps=1e-3, T=1.0):
+    """sde.py:251-252: [0, linspace(eps, T, steps)] cast to the state's fp32, as python floats."""
+    ts = torch.tensor(np.append(0.0, np.linspace(eps, T, steps))).float()
+    return [float(v) for v in ts]
+
+
+def em_plan(hs, steps, eps=1e-3, T=1.0, kind="sde", pred="noise_pred"):
+    """Coefficients of sde.euler_maruyama on ReverseSDE (kind='sde') or ODE (kind='ode') of the linear VP-SDE with
+    a noise-prediction net (sde.py:202-236 drift, 256-262 step): float64 [steps, 4], one row (t_net, a, b, c) per
+    step in the order the steps run (t = T first), such that
+
+        x' = a x + b eps_hat(x, t_net) + c z,   z ~ N(0, I)
+
+    With beta = beta_0 + t (beta_1 - beta_0), sigma_t = sqrt(cum_beta(t)) and dt = s - t < 0:
+        sde: a = 1 - beta dt / 2, b = beta dt / sigma_t,     c = sqrt(-beta dt)  (0 on the last step, s == 0)
+        ode: a = 1 - beta dt / 2, b = beta dt / (2 sigma_t), c = 0
+    and t_net = 999 t (ScoreModel.predict, sde.py:174)."""
+    if kind not in ("sde", "ode"):
+        raise ValueError(f"kind must be 'sde' or 'ode', got {kind!r}")
+    if pred != "noise_pred":
+        raise NotImplementedError(f"em_plan covers noise-prediction nets only (pred='noise_pred'), got {pred!r}")
+    if not isinstance(hs, HostLinear):
+        raise NotImplementedError("em_plan covers the linear VP schedule (HostLinear) only")
+    if int(steps) < 1:
+        raise ValueError("steps must be >= 1")
+    ts = em_grid(int(steps), eps, T)
+    rows = np.empty((len(ts) - 1, 4), dtype=np.float64)
+    for k, i in enumerate(range(len(ts) - 1, 0, -1)):
+        s, t = ts[i - 1], ts[i]
+        beta = hs.b0 + t * (hs.b1 - hs.b0)
+        sg = math.sqrt(-math.expm1(2.0 * hs.log_mean(t)))
+        dt = s - t
+        half = 1.0 if kind == "sde" else 0.5
+        c = math.sqrt(-beta * dt) if (kind == "sde" and s != 0.0) else 0.0
+        rows[k] = (999.0 * t, 1.0 - 0.5 * beta * dt, half * beta * dt / sg, c)
+    return rows
