@@ -348,7 +348,8 @@ int pdm_decoder_set_gn_fusion(int on);
  * Input img: fp32 [B, 3, S, S] (NCHW), S = latent_size * 2^(num_levels - 1) <= 512; output moments: fp32
  * [B, 8, latent, latent] (NCHW; mean = channels 0..3, logvar = 4..7).
  * Limits (create returns PDM_ERR_ARG otherwise): 1..4 levels, in_channels 3, z_channels 4 with double_z, every
- * channel count a multiple of 64 and <= 1024, latent_size a multiple of 8. */
+ * channel count a multiple of 64 and <= 1024, latent_size a multiple of 8 and <= 64: the mid AttnBlock's softmax
+ * takes at most 4096 = 64^2 tokens, so a one- or two-level encoder stops at image side 64 / 128 (not 512). */
 typedef struct pdm_encoder pdm_encoder;
 
 typedef struct pdm_encoder_cfg {
@@ -374,6 +375,52 @@ int pdm_encoder_encode_moments(pdm_encoder* e, const float* img, float* moments,
  * * noise); moments fp32 [B, 2C, hw], noise and z fp32 [B, C, hw] */
 int pdm_moments_sample(const float* moments, const float* noise, float* z, int B, int C, int hw, float scale,
                        void* stream);
+
+/* ---- the autoencoder's kernels on their own (exposed for parity tests) --------------------------------
+ * Caller-owned tensors, no decoder / encoder handle; each entry runs the launch code the decoder and the encoder run
+ * and returns PDM_ERR_ARG for a shape or alignment its kernel cannot take. */
+/* GroupNorm(32) [+ swish] (libs/autoencoder.py:31-32 Normalize, 26-28): x NHWC [B, P, C] fp32 or bf16 (x_dtype
+ * PDM_F32 / PDM_BF16), C % 32 == 0, C <= 1024 -> y bf16 [B, P, C] and stats fp32 [B, 32, 2] = (mean, rstd) per group.
+ * part (part_elems doubles; B * ceil(P / 64) * 64 always suffices) is the scratch of the statistics pass; with
+ * part_ready it instead holds ready-made partials [B, P / 256, 32, 2] = fp64 (sum, sum of squares) per 256-pixel
+ * chunk and group, the layout the GEMM epilogue below writes, and the statistics pass is skipped (P % 256 == 0). */
+int pdm_vae_groupnorm(const void* x, int x_dtype, int B, int P, int C, const float* gamma, const float* beta,
+                      float eps, int swish, double* part, long long part_elems, int part_ready, void* y, float* stats,
+                      void* stream);
+/* pdm_gemm_bf16 / pdm_gemm_conv3x3_bf16 whose output is a GroupNorm(32) input of gn_P rows per image (the conv: H * W):
+ * where the tile policy's epilogue can, it also writes the GroupNorm partials [M / gn_P, gn_P / 256, 32, 2] (fp64 sum,
+ * sum of squares of the stored values per 256-row chunk and group of N / 32 columns) to gn_part and sets *fused = 1;
+ * otherwise the product alone is computed, gn_part is left untouched and *fused = 0 (always so after
+ * pdm_decoder_set_gn_fusion off).  zero: >= 256 zero bytes of device memory (the padded taps' source). */
+int pdm_gemm_bf16_gn(const void* A1, int lda1, const void* A2, int lda2, int K1, const void* W, const float* bias,
+                     int M, int N, int K, int epi, void* out_bf16, int ldo, float* out_f32, int ldr, int accumulate,
+                     double* gn_part, int gn_P, int* fused, void* stream);
+int pdm_gemm_conv3x3_bf16_gn(const void* in, int B, int H, int W, int Cin, int up, const void* Wt, const float* bias,
+                             int N, int epi, void* out_bf16, float* out_f32, int accumulate, const void* zero,
+                             double* gn_part, int* fused, void* stream);
+/* AttnBlock softmax (libs/autoencoder.py:182-184): probs bf16 [rows, n] = softmax(scores fp32 [rows, n] * scale),
+ * n <= 4096 */
+int pdm_vae_softmax_rows(const float* scores, void* probs, long long rows, int n, float scale, void* stream);
+/* bf16 [B][n][ld] columns col0 .. col0 + C - 1 -> [B][C][n] (the AttnBlock's V^T); n % 32 == 0, C % 32 == 0 */
+int pdm_vae_transpose(const void* src, int ld, int col0, void* dst, int B, int n, int C, void* stream);
+/* decoder head: z fp32 [B, 4, h, w] (w <= 64) / scale_factor -> post_quant_conv (pq_w [4][4], pq_b [4]) -> conv_in
+ * (w [Cout][4][3][3], bias [Cout]) -> out fp32 NHWC [B, h, w, Cout] */
+int pdm_vae_dec_conv_in(const float* z, float scale_factor, const float* pq_w, const float* pq_b, const float* w,
+                        const float* bias, float* out, int B, int h, int wd, int Cout, void* stream);
+/* decoder conv_out: g bf16 NHWC [B, H, W, C], w bf16 [4][3][3][C] (rows >= out_ch unused), bias fp32 [4] -> img fp32
+ * NCHW [B, out_ch, H, W].  The MFMA kernel where it applies (C 64 / 128, W % 64 == 0, even H) unless force_valu */
+int pdm_vae_dec_conv_out(const void* g, int B, int H, int W, int C, const void* w, const float* bias, float* img,
+                         int out_ch, int force_valu, void* stream);
+/* encoder conv_in: img fp32 NCHW [B, 3, H, W] (W <= 512), w fp32 [C][3][3][3] (C % 16 == 0) -> out fp32 NHWC */
+int pdm_vae_enc_conv_in(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, int C,
+                        void* stream);
+/* encoder downsample operand: x fp32 NHWC [B, H, W, C] -> A bf16 [B * (H/2) * (W/2)][9 C] (columns (ky, kx, ci),
+ * source pixel (2y + ky, 2x + kx), zeros at row H / column W) */
+int pdm_vae_down_gather(const float* x, void* A, int B, int H, int W, int C, void* stream);
+/* encoder tail: conv_out (w bf16 [8][3][3][C], cbias [8]; C % 32 == 0) + quant_conv (qw [8][8], qb [8]) on g bf16 NHWC
+ * [B, H, W, C] -> moments fp32 NCHW [B, 8, H, W] */
+int pdm_vae_enc_tail(const void* g, int B, int H, int W, int C, const void* w, const float* cbias, const float* qw,
+                     const float* qb, float* moments, void* stream);
 
 /* ---- output stage (utils.sample2dir, utils.py:561-640) ------------------------------------------
  * Decoded images fp32 [B, C, H, W] -> uint8 [B, H, W, C]: unpreprocess (datasets.py:104-108) followed by

@@ -1,4 +1,4 @@
-"""ORACLE (test infrastructure): fp32 CPU restatement of FrozenAutoencoderKL.decode.
+"""ORACLE (test infrastructure): fp32 CPU restatement of FrozenAutoencoderKL.decode and .encode_moments.
 
 libs/autoencoder.py: Normalize = GroupNorm(32, eps=1e-6) (31-32), swish (26-28), Upsample nearest x2 +
 conv3x3 (35-50), ResnetBlock (75-134, temb None, nin_shortcut 1x1 when channels change), AttnBlock
@@ -40,6 +40,24 @@ def attn_block(sd, p, x):
     w = torch.softmax(torch.bmm(q, k) * (int(c) ** -0.5), dim=2)
     o = torch.bmm(v.reshape(b, c, hh * ww), w.permute(0, 2, 1)).reshape(b, c, hh, ww)
     return x + _conv(sd, f"{p}.proj_out", o, 0)
+
+
+def encode_moments(sd, x, ch_mult=(1, 2, 4, 4), num_res_blocks=2, prefix="encoder"):
+    """FrozenAutoencoderKL.encode_moments (428-431) = Encoder.forward (275-300: conv_in, per level the ResnetBlocks
+    and -- but for the last -- Downsample (65-69: zero pad right / bottom by one, 3x3 stride 2), mid, norm_out, swish,
+    conv_out) -> quant_conv."""
+    h = _conv(sd, f"{prefix}.conv_in", x, 1)
+    for i_level in range(len(ch_mult)):
+        for i_block in range(num_res_blocks):
+            h = resnet_block(sd, f"{prefix}.down.{i_level}.block.{i_block}", h)
+        if i_level != len(ch_mult) - 1:
+            p = f"{prefix}.down.{i_level}.downsample.conv"
+            h = F.conv2d(F.pad(h, (0, 1, 0, 1)), sd[f"{p}.weight"], sd[f"{p}.bias"], stride=2)
+    h = resnet_block(sd, f"{prefix}.mid.block_1", h)
+    h = attn_block(sd, f"{prefix}.mid.attn_1", h)
+    h = resnet_block(sd, f"{prefix}.mid.block_2", h)
+    h = _conv(sd, f"{prefix}.conv_out", _swish(_gn(sd, f"{prefix}.norm_out", h)), 1)
+    return _conv(sd, "quant_conv", h, 0)
 
 
 def decode(sd, z, scale_factor=0.18215, ch_mult=(1, 2, 4, 4), num_res_blocks=2, prefix="decoder"):

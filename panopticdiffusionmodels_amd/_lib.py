@@ -196,6 +196,33 @@ _SIGS = {
                                                   ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "pdm_moments_sample": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
+    # the autoencoder's kernels on their own (include/pdm.h, parity tests)
+    "pdm_vae_groupnorm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p]),
+    "pdm_gemm_bf16_gn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                        ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                        ctypes.c_void_p]),
+    "pdm_gemm_conv3x3_bf16_gn": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int),
+                                                ctypes.c_void_p]),
+    "pdm_vae_softmax_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                            ctypes.c_float, ctypes.c_void_p]),
+    "pdm_vae_transpose": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "pdm_vae_dec_conv_in": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_float] + [ctypes.c_void_p] * 5 +
+                            [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "pdm_vae_dec_conv_out": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_void_p]),
+    "pdm_vae_enc_conv_in": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "pdm_vae_down_gather": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "pdm_vae_enc_tail": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] * 6),
     # training step (include/pdm.h "training")
     "pdm_train_create": (ctypes.c_int, [ctypes.POINTER(PdmUvitCfg), ctypes.POINTER(ctypes.c_void_p)]),
     "pdm_train_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -485,6 +512,139 @@ def gemm_conv3x3(x, w, bias=None, epi=EPI_F32, up=0, out=None, out_f32=None, acc
     check(lib.pdm_gemm_conv3x3_bf16(ptr(x), B, H, W, C, up, ptr(wk), ptr(bias), N, epi, ptr(out), ptr(out_f32),
                                     int(accumulate), stream_ptr(x.device)), "pdm_gemm_conv3x3_bf16")
     return out_f32 if epi == EPI_F32 else out
+
+
+# ---- the autoencoder's kernels on their own (include/pdm.h pdm_vae_*, parity tests) -------------------
+
+def gn_part_elems(B, gn_P):
+    """doubles in the GroupNorm partials [B, gn_P / 256, 32, 2] a GEMM epilogue writes."""
+    return B * (gn_P // 256) * 64
+
+
+def vae_groupnorm(x, gamma, beta, eps=1e-6, swish=False, partials=None):
+    """GroupNorm(32) [+ swish] of NHWC x [B, P, C] (fp32 / bf16) -> (y bf16 [B, P, C], stats fp32 [B, 32, 2]).
+    partials: ready-made fp64 [B, P / 256, 32, 2] (sum, sum of squares), replacing the statistics pass."""
+    lib = load()
+    require_gpu(x)
+    B, P, C = x.shape
+    y = torch.empty(B, P, C, dtype=torch.bfloat16, device=x.device)
+    stats = torch.empty(B, 32, 2, dtype=torch.float32, device=x.device)
+    part = partials if partials is not None else torch.empty(B * ((P + 63) // 64) * 64, dtype=torch.float64,
+                                                             device=x.device)
+    check(lib.pdm_vae_groupnorm(ptr(x), PDM_F32 if x.dtype == torch.float32 else PDM_BF16, B, P, C, ptr(gamma),
+                                ptr(beta), eps, int(swish), ptr(part), part.numel(), int(partials is not None), ptr(y),
+                                ptr(stats), stream_ptr(x.device)), "pdm_vae_groupnorm")
+    return y, stats
+
+
+def gemm_gn(a, w, bias, epi, gn_part, gn_P, out=None, out_f32=None, accumulate=False):
+    """pdm_gemm_bf16_gn: gemm() whose epilogue also writes the GroupNorm partials to gn_part (fp64) where the tile
+    policy can.  Returns (output, fused)."""
+    lib = load()
+    require_gpu(a)
+    M, K = a.shape
+    N = w.shape[0]
+    if epi == EPI_BF16 and out is None:
+        out = torch.empty(M, N, dtype=torch.bfloat16, device=a.device)
+    if epi == EPI_F32 and out_f32 is None:
+        out_f32 = torch.zeros(M, N, dtype=torch.float32, device=a.device)
+    fused = ctypes.c_int(-1)
+    check(lib.pdm_gemm_bf16_gn(ptr(a), a.stride(0), None, 0, K, ptr(w), ptr(bias), M, N, K, epi, ptr(out),
+                               out.stride(0) if out is not None else 0, ptr(out_f32),
+                               out_f32.stride(0) if out_f32 is not None else 0, int(accumulate), ptr(gn_part), gn_P,
+                               ctypes.byref(fused), stream_ptr(a.device)), "pdm_gemm_bf16_gn")
+    return (out_f32 if epi == EPI_F32 else out), fused.value
+
+
+def gemm_conv3x3_gn(x, w, bias, epi, gn_part, up=0, out=None, out_f32=None, accumulate=False):
+    """pdm_gemm_conv3x3_bf16_gn: gemm_conv3x3() with the GroupNorm partials of its output (H * W rows per image).
+    Returns (output, fused)."""
+    lib = load()
+    require_gpu(x)
+    B, h, wd, C = x.shape
+    H, W = h << up, wd << up
+    N = w.shape[0]
+    wk = w.permute(0, 2, 3, 1).reshape(N, 9 * C).contiguous()
+    if epi == EPI_BF16 and out is None:
+        out = torch.empty(B * H * W, N, dtype=torch.bfloat16, device=x.device)
+    if epi == EPI_F32 and out_f32 is None:
+        out_f32 = torch.zeros(B * H * W, N, dtype=torch.float32, device=x.device)
+    zero = torch.zeros(256, dtype=torch.uint8, device=x.device)
+    fused = ctypes.c_int(-1)
+    check(lib.pdm_gemm_conv3x3_bf16_gn(ptr(x), B, H, W, C, up, ptr(wk), ptr(bias), N, epi, ptr(out), ptr(out_f32),
+                                       int(accumulate), ptr(zero), ptr(gn_part), ctypes.byref(fused),
+                                       stream_ptr(x.device)), "pdm_gemm_conv3x3_bf16_gn")
+    return (out_f32 if epi == EPI_F32 else out), fused.value
+
+
+def vae_softmax_rows(scores, scale):
+    """bf16 softmax(scores * scale) over the last dim of fp32 scores [rows, n], n <= 4096."""
+    require_gpu(scores)
+    rows, n = scores.shape
+    p = torch.empty(rows, n, dtype=torch.bfloat16, device=scores.device)
+    check(load().pdm_vae_softmax_rows(ptr(scores), ptr(p), rows, n, scale, stream_ptr(scores.device)),
+          "pdm_vae_softmax_rows")
+    return p
+
+
+def vae_transpose(src, col0, C):
+    """bf16 src [B, n, ld] columns col0 .. col0 + C - 1 -> [B, C, n]."""
+    require_gpu(src)
+    B, n, ld = src.shape
+    dst = torch.empty(B, C, n, dtype=torch.bfloat16, device=src.device)
+    check(load().pdm_vae_transpose(ptr(src), ld, col0, ptr(dst), B, n, C, stream_ptr(src.device)), "pdm_vae_transpose")
+    return dst
+
+
+def vae_dec_conv_in(z, scale_factor, pq_w, pq_b, w, bias):
+    """z fp32 [B, 4, h, w] / scale_factor -> post_quant_conv -> conv_in (w [Cout, 4, 3, 3]) -> fp32 NHWC."""
+    require_gpu(z)
+    B, _, h, wd = z.shape
+    Cout = w.shape[0]
+    out = torch.empty(B, h, wd, Cout, dtype=torch.float32, device=z.device)
+    check(load().pdm_vae_dec_conv_in(ptr(z), scale_factor, ptr(pq_w), ptr(pq_b), ptr(w), ptr(bias), ptr(out), B, h, wd,
+                                     Cout, stream_ptr(z.device)), "pdm_vae_dec_conv_in")
+    return out
+
+
+def vae_dec_conv_out(g, w, bias, out_ch=3, force_valu=False):
+    """g bf16 NHWC [B, H, W, C], w bf16 [4, 3, 3, C] (ky, kx, ci), bias fp32 [4] -> fp32 NCHW [B, out_ch, H, W]."""
+    require_gpu(g)
+    B, H, W, C = g.shape
+    img = torch.empty(B, out_ch, H, W, dtype=torch.float32, device=g.device)
+    check(load().pdm_vae_dec_conv_out(ptr(g), B, H, W, C, ptr(w), ptr(bias), ptr(img), out_ch, int(force_valu),
+                                      stream_ptr(g.device)), "pdm_vae_dec_conv_out")
+    return img
+
+
+def vae_enc_conv_in(img, w, bias):
+    """img fp32 NCHW [B, 3, H, W], w fp32 [C, 3, 3, 3] -> fp32 NHWC [B, H, W, C]."""
+    require_gpu(img)
+    B, _, H, W = img.shape
+    C = w.shape[0]
+    out = torch.empty(B, H, W, C, dtype=torch.float32, device=img.device)
+    check(load().pdm_vae_enc_conv_in(ptr(img), ptr(w), ptr(bias), ptr(out), B, H, W, C, stream_ptr(img.device)),
+          "pdm_vae_enc_conv_in")
+    return out
+
+
+def vae_down_gather(x):
+    """x fp32 NHWC [B, H, W, C] -> the stride-2 downsample's GEMM operand bf16 [B * (H/2) * (W/2), 9 C]."""
+    require_gpu(x)
+    B, H, W, C = x.shape
+    A = torch.empty(B * (H // 2) * (W // 2), 9 * C, dtype=torch.bfloat16, device=x.device)
+    check(load().pdm_vae_down_gather(ptr(x), ptr(A), B, H, W, C, stream_ptr(x.device)), "pdm_vae_down_gather")
+    return A
+
+
+def vae_enc_tail(g, w, cbias, qw, qb):
+    """g bf16 NHWC [B, H, W, C], conv_out w bf16 [8, 3, 3, C] + quant_conv qw [8, 8] -> moments fp32 [B, 8, H, W]."""
+    require_gpu(g)
+    B, H, W, C = g.shape
+    m = torch.empty(B, 8, H, W, dtype=torch.float32, device=g.device)
+    check(load().pdm_vae_enc_tail(ptr(g), B, H, W, C, ptr(w), ptr(cbias), ptr(qw), ptr(qb), ptr(m),
+                                  stream_ptr(g.device)), "pdm_vae_enc_tail")
+    return m
 
 
 def gemm_batched(a, w, bias=None, epi=EPI_F32):

@@ -341,6 +341,88 @@ __global__ __launch_bounds__(256) void conv_out_mfma_kernel(const bf16* g, int H
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Launches: grid, shared-memory size and kernel choice of every kernel above, each in ONE place -- the decoder /
+// encoder orchestration below and the pdm_vae_* entry points (parity tests on caller-owned tensors) both go through
+// them.  Each returns hipErrorInvalidValue for a shape its kernel cannot take.
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// GroupNorm(32): statistics pass (skipped with part_ready: `part` then holds partials in 256-pixel chunks, as the GEMM
+// epilogue leaves them), (mean, rstd) -> stats [B, 32, 2], apply -> y.  part: B * gn_chunks(P, C, part_ready) * 64
+// doubles.
+inline int gn_chunks(int P, int C, bool part_ready) {
+  const int pix = part_ready ? 256 : gn_pix(C);
+  return (P + pix - 1) / pix;
+}
+inline bool gn_shape_ok(int B, int P, int C) {
+  // gn_partial_kernel: one thread per channel quad, >= 1 pixel plane per block, red[] holds planes * C <= 1024 sums;
+  // gn_apply_kernel: one thread per channel octet; blockIdx.y = image
+  return B > 0 && B <= 65535 && P > 0 && C > 0 && C % 32 == 0 && C <= 1024;
+}
+template <typename T>
+hipError_t gn_launch(const T* x, int B, int P, int C, const float* gamma, const float* beta, float eps, bool swish,
+                     double* part, bool part_ready, float* stats, bf16* y, hipStream_t s) {
+  if (!gn_shape_ok(B, P, C) || (part_ready && P % 256)) return hipErrorInvalidValue;
+  const int pix = part_ready ? 256 : gn_pix(C);
+  const int nchunk = gn_chunks(P, C, part_ready);
+  if (!part_ready)
+    hipLaunchKernelGGL(gn_partial_kernel<T>, dim3(nchunk, B), dim3(256), 0, s, x, P, C, nchunk, pix, part);
+  hipLaunchKernelGGL(gn_final_kernel, dim3((B * 32 + 3) / 4), dim3(256), 0, s, part, nchunk, (double)P * (C / 32), eps,
+                     stats, B);
+  const int planes = 256 / (C / 8);
+  // >= ~8192 blocks (up to 32 waves per CU): the pixel loop keeps 4 pixels' loads in flight per thread, and at
+  // ~2048 blocks the fp32 apply streamed at ~2.5 TB/s (512^2 decode, profiles/r03r_dec512_kernel_stats.csv)
+  const int gx = std::max(1, std::min((P + planes - 1) / planes, 8192 / B + 1));
+  hipLaunchKernelGGL(gn_apply_kernel<T>, dim3(gx, B), dim3(256), 0, s, x, stats, gamma, beta, y, P, C, swish ? 1 : 0);
+  return hipGetLastError();
+}
+
+// decoder z -> post_quant_conv -> conv_in: the LDS rows hold w + 2 <= 66 pixels
+hipError_t dec_conv_in_launch(const float* z, float scale_factor, const float* pq_w, const float* pq_b, const float* w,
+                              const float* bias, float* out, int B, int h, int wd, int Cout, hipStream_t s) {
+  if (B <= 0 || B > 65535 || h <= 0 || wd <= 0 || wd > 64 || Cout <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(conv_in_kernel, dim3(h, B), dim3(256), 0, s, z, 1.0f / scale_factor, pq_w, pq_b, w, bias, out, h,
+                     wd, Cout);
+  return hipGetLastError();
+}
+
+// row softmax: a row lives in 16 registers x 256 threads
+hipError_t softmax_rows_launch(const float* sc, bf16* p, long long rows, int n, float scale, hipStream_t s) {
+  if (rows <= 0 || rows > 0x7fffffffLL || n <= 0 || n > 4096) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)rows), dim3(256), 0, s, sc, p, n, scale);
+  return hipGetLastError();
+}
+
+// [B][n][ld] columns col0 .. col0 + C -> [B][C][n]: whole 32 x 32 tiles only
+hipError_t transpose_launch(const bf16* src, int ld, int col0, bf16* dst, int B, int n, int C, hipStream_t s) {
+  if (B <= 0 || B > 65535 || n <= 0 || n % 32 || C <= 0 || C % 32 || C / 32 > 65535 || col0 < 0 || col0 + C > ld)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(transpose_kernel, dim3(n / 32, C / 32, B), dim3(256), 0, s, src, ld, col0, dst, n, C);
+  return hipGetLastError();
+}
+
+// decoder conv_out: the MFMA kernel for C in {64, 128} on whole 64-pixel segments and row pairs (every shipped
+// decoder), else -- or with force_valu (parity tests) -- the VALU kernel, whose fp32 weights take 9 * C * 16 bytes of
+// dynamic LDS
+inline bool conv_out_mfma(int B, int H, int W, int C, bool force_valu) {
+  return !force_valu && (C == 128 || C == 64) && W % 64 == 0 && H % 2 == 0 && B <= 65535;
+}
+hipError_t conv_out_launch(const bf16* g, int B, int H, int W, int C, const bf16* w, const float* bias, float* img,
+                           int out_ch, bool force_valu, hipStream_t s) {
+  if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || C % 8 || out_ch < 1 || out_ch > 4) return hipErrorInvalidValue;
+  const bool mfma = conv_out_mfma(B, H, W, C, force_valu);
+  if (mfma && C == 128)
+    hipLaunchKernelGGL(conv_out_mfma_kernel<128>, dim3(H / 2, B), dim3(256), 0, s, g, H, W, w, bias, img, out_ch);
+  else if (mfma)
+    hipLaunchKernelGGL(conv_out_mfma_kernel<64>, dim3(H / 2, B), dim3(256), 0, s, g, H, W, w, bias, img, out_ch);
+  else {
+    const long long npix = (long long)B * H * W;
+    hipLaunchKernelGGL(conv_out_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 9 * C * 16, s, g, B, H, W, C, w,
+                       bias, img, out_ch);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 }  // namespace pdm
 
@@ -476,20 +558,9 @@ int groupnorm(const DCtx& c, const T* x, int B, int P, int C, const std::string&
   // statistics pass: skipped when the producing epilogue already left the partials (one read of x fewer)
   const bool pre = *c.gn_ready;
   *c.gn_ready = false;
-  const int pix = pre ? 256 : pdm::gn_pix(C);
-  const int nchunk = (P + pix - 1) / pix;
-  if (!pre)
-    hipLaunchKernelGGL(pdm::gn_partial_kernel<T>, dim3(nchunk, B), dim3(256), 0, c.s, x, P, C, nchunk, pix, c.w->part);
-  hipLaunchKernelGGL(pdm::gn_final_kernel, dim3((B * 32 + 3) / 4), dim3(256), 0, c.s, c.w->part, nchunk,
-                     (double)P * (C / 32), 1e-6f, c.w->stats, B);
-  if (C % 8 || C > 2048) return dfail(PDM_ERR_ARG, "decoder: GroupNorm needs C % 8 == 0 and C <= 2048");
-  const int planes = 256 / (C / 8);
-  // >= ~8192 blocks (up to 32 waves per CU): the pixel loop keeps 4 pixels' loads in flight per thread, and at
-  // ~2048 blocks the fp32 apply streamed at ~2.5 TB/s (512^2 decode, profiles/r03r_dec512_kernel_stats.csv)
-  const int gx = std::max(1, std::min((P + planes - 1) / planes, 8192 / B + 1));
-  hipLaunchKernelGGL(pdm::gn_apply_kernel<T>, dim3(gx, B), dim3(256), 0, c.s, x, c.w->stats,
-                     c.d->f(norm + ".weight"), c.d->f(norm + ".bias"), y, P, C, swish ? 1 : 0);
-  D_HIP(hipGetLastError());
+  if (!pdm::gn_shape_ok(B, P, C)) return dfail(PDM_ERR_ARG, "decoder: GroupNorm needs C % 32 == 0 and C <= 1024");
+  D_HIP(pdm::gn_launch<T>(x, B, P, C, c.d->f(norm + ".weight"), c.d->f(norm + ".bias"), 1e-6f, swish, c.w->part, pre,
+                          c.w->stats, y, c.s));
   return PDM_OK;
 }
 
@@ -498,25 +569,38 @@ bool g_gn_fusion = true;   // pdm_decoder_set_gn_fusion
 
 // gn_P > 0: the output is the next GroupNorm's input (gn_P pixels per image): its epilogue also writes the GroupNorm
 // partials where it can (pdm::gemm_gn_fusable; c.gn_ready tells the GroupNorm)
-int launch_gn(const DCtx& c, pdm::GemmArgs& a, int epi, int gn_P) {
+// (shared with pdm_gemm_bf16_gn / pdm_gemm_conv3x3_bf16_gn; *fused: whether the epilogue wrote `part`)
+int gemm_gn(pdm::GemmArgs& a, int epi, double* part, int gn_P, hipStream_t s, bool* fused) {
   if (gn_P > 0 && g_gn_fusion) {
-    a.gn_part = c.w->part; a.gn_P = gn_P; a.gn_cpg = a.N / 32;
+    a.gn_part = part; a.gn_P = gn_P; a.gn_cpg = a.N / 32;
     if (!pdm::gemm_gn_fusable(a, epi)) a.gn_part = nullptr;
   }
   D_CHECK(pdm::gemm_check(a, epi));
-  D_HIP(pdm::gemm_launch(a, epi, c.s));
-  *c.gn_ready = a.gn_part != nullptr;
+  D_HIP(pdm::gemm_launch(a, epi, s));
+  *fused = a.gn_part != nullptr;
   return PDM_OK;
+}
+
+int launch_gn(const DCtx& c, pdm::GemmArgs& a, int epi, int gn_P) {
+  return gemm_gn(a, epi, c.w->part, gn_P, c.s, c.gn_ready);
+}
+
+// the implicit-GEMM operands of a conv3x3 over a B x H x W output grid (H, W after the optional x2 upsample)
+pdm::GemmArgs conv3_args(const bf16* in, int B, int H, int W, int cin, int up, const bf16* wt, const float* bias,
+                         int cout, bf16* ob, float* of, int accumulate, const bf16* zero) {
+  pdm::GemmArgs a{};
+  a.A1 = in; a.lda1 = cin; a.K1 = 9 * cin;
+  a.W = wt; a.bias = bias;
+  a.M = B * H * W; a.N = cout; a.K = 9 * cin;
+  a.out_bf16 = ob; a.ldo = cout; a.out_f32 = of; a.ldr = cout; a.accumulate = accumulate;
+  a.conv = 1; a.convH = H; a.convW = W; a.convC = cin; a.conv_up = up; a.zero = zero;
+  return a;
 }
 
 int conv3(const DCtx& c, const bf16* in, int B, int res, int cin, int cout, const std::string& name, int epi,
           bf16* ob, float* of, int accumulate, int up = 0, bool gn = false) {
-  pdm::GemmArgs a{};
-  a.A1 = in; a.lda1 = cin; a.K1 = 9 * cin;
-  a.W = c.d->w(name + ".weight"); a.bias = c.d->f(name + ".bias");
-  a.M = B * res * res; a.N = cout; a.K = 9 * cin;
-  a.out_bf16 = ob; a.ldo = cout; a.out_f32 = of; a.ldr = cout; a.accumulate = accumulate;
-  a.conv = 1; a.convH = res; a.convW = res; a.convC = cin; a.conv_up = up; a.zero = c.w->zero;
+  pdm::GemmArgs a = conv3_args(in, B, res, res, cin, up, c.d->w(name + ".weight"), c.d->f(name + ".bias"), cout, ob, of,
+                               accumulate, c.w->zero);
   return launch_gn(c, a, epi, gn ? res * res : 0);
 }
 
@@ -573,9 +657,8 @@ int attnblock(const DCtx& c, float* X, int B, int res, int C, const std::string&
     D_CHECK(pdm::gemm_check(a, pdm::EPI_F32));
     D_HIP(pdm::gemm_launch(a, pdm::EPI_F32, c.s));
   }
-  hipLaunchKernelGGL(pdm::softmax_rows_kernel, dim3(B * hw), dim3(256), 0, c.s, w.S, w.P, hw, 1.0f / sqrtf((float)C));
-  hipLaunchKernelGGL(pdm::transpose_kernel, dim3(hw / 32, C / 32, B), dim3(256), 0, c.s, w.QKV, 3 * C, 2 * C, w.VT, hw, C);
-  D_HIP(hipGetLastError());
+  D_HIP(pdm::softmax_rows_launch(w.S, w.P, (long long)B * hw, hw, 1.0f / sqrtf((float)C), c.s));
+  D_HIP(pdm::transpose_launch(w.QKV, 3 * C, 2 * C, w.VT, B, hw, C, c.s));
   {  // O[b] = P[b] V[b]  with V^T as the [N][K] operand
     pdm::GemmArgs a{};
     a.A1 = w.P; a.lda1 = hw; a.K1 = hw;
@@ -697,10 +780,8 @@ int pdm_decoder_decode(pdm_decoder* d, const float* z, float* img, int B, void* 
   int res = d->h0;
   float* X = w.X;
   float* X2 = w.X2;
-  hipLaunchKernelGGL(pdm::conv_in_kernel, dim3(res, B), dim3(256), 0, s, z, 1.0f / d->cfg.scale_factor,
-                     d->f("post_quant_conv.weight"), d->f("post_quant_conv.bias"), d->f("decoder.conv_in.weight"),
-                     d->f("decoder.conv_in.bias"), X, res, res, T);
-  D_HIP(hipGetLastError());
+  D_HIP(pdm::dec_conv_in_launch(z, d->cfg.scale_factor, d->f("post_quant_conv.weight"), d->f("post_quant_conv.bias"),
+                                d->f("decoder.conv_in.weight"), d->f("decoder.conv_in.bias"), X, B, res, res, T, s));
   D_TRY(resblock(c, X, X2, B, res, T, T, "decoder.mid.block_1"));
   D_TRY(attnblock(c, X, B, res, T, "decoder.mid.attn_1"));
   D_TRY(resblock(c, X, X2, B, res, T, T, "decoder.mid.block_2"));
@@ -730,21 +811,8 @@ int pdm_decoder_decode(pdm_decoder* d, const float* z, float* img, int B, void* 
     }
   }
   D_TRY(groupnorm<float>(c, X, B, res * res, cin, "decoder.norm_out", w.G, true));
-  {
-    const long long npix = (long long)B * res * res;
-    const bf16* cw = d->w("decoder.conv_out.weight");
-    const float* cb = d->f("decoder.conv_out.bias");
-    if (cin == 128 && res % 64 == 0)
-      hipLaunchKernelGGL(pdm::conv_out_mfma_kernel<128>, dim3(res / 2, B), dim3(256), 0, s, w.G, res, res, cw, cb, img,
-                         d->cfg.out_ch);
-    else if (cin == 64 && res % 64 == 0)
-      hipLaunchKernelGGL(pdm::conv_out_mfma_kernel<64>, dim3(res / 2, B), dim3(256), 0, s, w.G, res, res, cw, cb, img,
-                         d->cfg.out_ch);
-    else
-      hipLaunchKernelGGL(pdm::conv_out_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 9 * cin * 16, s, w.G,
-                         B, res, res, cin, cw, cb, img, d->cfg.out_ch);
-  }
-  D_HIP(hipGetLastError());
+  D_HIP(pdm::conv_out_launch(w.G, B, res, res, cin, d->w("decoder.conv_out.weight"), d->f("decoder.conv_out.bias"), img,
+                             d->cfg.out_ch, false, s));
   return PDM_OK;
 }
 
@@ -835,6 +903,10 @@ int pdm_encoder_create(const pdm_encoder_cfg* cfg, pdm_encoder** out) {
   if (c.latent_size <= 0 || c.latent_size % 8 || (c.latent_size << (c.num_levels - 1)) > 512)
     return dfail(PDM_ERR_ARG, "encoder: latent size must be a multiple of 8 and the image side "
                               "latent * 2^(levels - 1) at most 512");
+  // the mid AttnBlock's row softmax holds a row of latent^2 scores in registers (softmax_rows_launch): without this a
+  // one- or two-level encoder above latent 64 would normalise over the first 4096 keys only
+  if (c.latent_size > 64)
+    return dfail(PDM_ERR_ARG, "encoder: latent size must be <= 64 (the attention softmax takes at most 4096 tokens)");
   pdm_encoder* e = new pdm_encoder();
   e->cfg = c;
   e->nlev = c.num_levels;
@@ -944,6 +1016,139 @@ int pdm_moments_sample(const float* moments, const float* noise, float* z, int B
   if (!moments || !noise || !z || B <= 0 || C <= 0 || hw <= 0)
     return dfail(PDM_ERR_ARG, "pdm_moments_sample: bad argument");
   D_HIP(pdm::moments_sample_launch(moments, noise, z, B, C, hw, scale, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+// ---- the autoencoder's kernels on caller-owned tensors (parity tests): each entry validates what its kernel assumes
+// and then runs the launch function the decoder / encoder run ----------------------------------------------------------
+#define V_ARG(cond, msg) \
+  do {                   \
+    if (!(cond)) return dfail(PDM_ERR_ARG, msg); \
+  } while (0)
+
+int pdm_vae_groupnorm(const void* x, int x_dtype, int B, int P, int C, const float* gamma, const float* beta,
+                      float eps, int swish, double* part, long long part_elems, int part_ready, void* y, float* stats,
+                      void* stream) {
+  V_ARG(x && gamma && beta && part && y && stats, "pdm_vae_groupnorm: null argument");
+  V_ARG(x_dtype == PDM_F32 || x_dtype == PDM_BF16, "pdm_vae_groupnorm: x must be fp32 or bf16");
+  V_ARG(pdm::gn_shape_ok(B, P, C), "pdm_vae_groupnorm: needs B in 1..65535, P > 0, C % 32 == 0 and C <= 1024");
+  V_ARG(!part_ready || P % 256 == 0, "pdm_vae_groupnorm: ready-made partials come in whole 256-pixel chunks");
+  V_ARG(part_elems >= (long long)B * pdm::gn_chunks(P, C, part_ready != 0) * 64,
+        "pdm_vae_groupnorm: partials buffer too small");
+  V_ARG(pdm::al16(x) && pdm::al16(y) && ((uintptr_t)part & 7) == 0 && ((uintptr_t)stats & 3) == 0,
+        "pdm_vae_groupnorm: x and y must be 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  if (x_dtype == PDM_F32)
+    D_HIP(pdm::gn_launch<float>((const float*)x, B, P, C, gamma, beta, eps, swish != 0, part, part_ready != 0, stats,
+                                (bf16*)y, s));
+  else
+    D_HIP(pdm::gn_launch<bf16>((const bf16*)x, B, P, C, gamma, beta, eps, swish != 0, part, part_ready != 0, stats,
+                               (bf16*)y, s));
+  return PDM_OK;
+}
+
+int pdm_gemm_bf16_gn(const void* A1, int lda1, const void* A2, int lda2, int K1, const void* W, const float* bias, int M,
+                     int N, int K, int epi, void* out_bf16, int ldo, float* out_f32, int ldr, int accumulate,
+                     double* gn_part, int gn_P, int* fused, void* stream) {
+  V_ARG(gn_part && fused && gn_P > 0, "pdm_gemm_bf16_gn: gn_part, fused and a positive gn_P are required");
+  pdm::GemmArgs a{};
+  a.A1 = (const bf16*)A1; a.lda1 = lda1;
+  a.A2 = (const bf16*)A2; a.lda2 = lda2;
+  a.K1 = A2 ? K1 : K;
+  a.W = (const bf16*)W; a.bias = bias;
+  a.M = M; a.N = N; a.K = K;
+  a.out_bf16 = (bf16*)out_bf16; a.ldo = ldo;
+  a.out_f32 = out_f32; a.ldr = ldr;
+  a.accumulate = accumulate;
+  bool f = false;
+  *fused = 0;
+  D_TRY(gemm_gn(a, epi, gn_part, gn_P, (hipStream_t)stream, &f));
+  *fused = f ? 1 : 0;
+  return PDM_OK;
+}
+
+int pdm_gemm_conv3x3_bf16_gn(const void* in, int B, int H, int W, int Cin, int up, const void* Wt, const float* bias,
+                             int N, int epi, void* out_bf16, float* out_f32, int accumulate, const void* zero,
+                             double* gn_part, int* fused, void* stream) {
+  V_ARG(gn_part && fused && zero, "pdm_gemm_conv3x3_bf16_gn: gn_part, fused and the zero page are required");
+  V_ARG(B > 0 && H > 0 && W > 0 && (long long)B * H * W <= 0x7fffffffLL, "pdm_gemm_conv3x3_bf16_gn: bad shape");
+  pdm::GemmArgs a = conv3_args((const bf16*)in, B, H, W, Cin, up, (const bf16*)Wt, bias, N, (bf16*)out_bf16, out_f32,
+                               accumulate, (const bf16*)zero);
+  bool f = false;
+  *fused = 0;
+  D_TRY(gemm_gn(a, epi, gn_part, H * W, (hipStream_t)stream, &f));
+  *fused = f ? 1 : 0;
+  return PDM_OK;
+}
+
+int pdm_vae_softmax_rows(const float* scores, void* probs, long long rows, int n, float scale, void* stream) {
+  V_ARG(scores && probs, "pdm_vae_softmax_rows: null argument");
+  V_ARG(rows > 0 && rows <= 0x7fffffffLL, "pdm_vae_softmax_rows: bad row count");
+  V_ARG(n > 0 && n <= 4096, "pdm_vae_softmax_rows: a row holds 1..4096 columns");
+  D_HIP(pdm::softmax_rows_launch(scores, (bf16*)probs, rows, n, scale, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_vae_transpose(const void* src, int ld, int col0, void* dst, int B, int n, int C, void* stream) {
+  V_ARG(src && dst, "pdm_vae_transpose: null argument");
+  V_ARG(B > 0 && B <= 65535 && n > 0 && n % 32 == 0 && C > 0 && C % 32 == 0 && C / 32 <= 65535,
+        "pdm_vae_transpose: needs n % 32 == 0 and C % 32 == 0");
+  V_ARG(col0 >= 0 && col0 + C <= ld, "pdm_vae_transpose: the column block must lie inside a row");
+  D_HIP(pdm::transpose_launch((const bf16*)src, ld, col0, (bf16*)dst, B, n, C, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_vae_dec_conv_in(const float* z, float scale_factor, const float* pq_w, const float* pq_b, const float* w,
+                        const float* bias, float* out, int B, int h, int wd, int Cout, void* stream) {
+  V_ARG(z && pq_w && pq_b && w && bias && out, "pdm_vae_dec_conv_in: null argument");
+  V_ARG(scale_factor != 0.f, "pdm_vae_dec_conv_in: scale_factor must not be 0");
+  V_ARG(B > 0 && B <= 65535 && h > 0 && wd > 0 && Cout > 0, "pdm_vae_dec_conv_in: bad shape");
+  V_ARG(wd <= 64, "pdm_vae_dec_conv_in: latent width must be <= 64");
+  D_HIP(pdm::dec_conv_in_launch(z, scale_factor, pq_w, pq_b, w, bias, out, B, h, wd, Cout, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_vae_dec_conv_out(const void* g, int B, int H, int W, int C, const void* w, const float* bias, float* img,
+                         int out_ch, int force_valu, void* stream) {
+  V_ARG(g && w && bias && img, "pdm_vae_dec_conv_out: null argument");
+  V_ARG(B > 0 && H > 0 && W > 0 && out_ch >= 1 && out_ch <= 4, "pdm_vae_dec_conv_out: bad shape (out_ch 1..4)");
+  V_ARG(C > 0 && C % 8 == 0, "pdm_vae_dec_conv_out: C must be a multiple of 8");
+  V_ARG((long long)H * W * C * 2 < 0x7fffffffLL, "pdm_vae_dec_conv_out: one image must stay below 2 GiB");
+  V_ARG(pdm::al16(g) && pdm::al16(w) && pdm::al16(img), "pdm_vae_dec_conv_out: g, w and img must be 16-byte aligned");
+  V_ARG(pdm::conv_out_mfma(B, H, W, C, force_valu != 0) || 9 * C * 16 <= 65536,
+        "pdm_vae_dec_conv_out: the VALU kernel's weights need 9 * C * 16 bytes <= 64 KiB");
+  D_HIP(pdm::conv_out_launch((const bf16*)g, B, H, W, C, (const bf16*)w, bias, img, out_ch, force_valu != 0,
+                             (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_vae_enc_conv_in(const float* img, const float* w, const float* bias, float* out, int B, int H, int W, int C,
+                        void* stream) {
+  V_ARG(img && w && bias && out, "pdm_vae_enc_conv_in: null argument");
+  V_ARG(B > 0 && B <= 65535 && H > 0 && W > 0 && C > 0, "pdm_vae_enc_conv_in: bad shape");
+  V_ARG(W <= 512 && C % 16 == 0 && (C + 255) / 256 <= 65535, "pdm_vae_enc_conv_in: needs W <= 512 and C % 16 == 0");
+  V_ARG(pdm::al16(out) && pdm::al16(bias), "pdm_vae_enc_conv_in: out and bias must be 16-byte aligned");
+  D_HIP(pdm::enc_conv_in_launch(img, w, bias, out, B, H, W, C, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_vae_down_gather(const float* x, void* A, int B, int H, int W, int C, void* stream) {
+  V_ARG(x && A, "pdm_vae_down_gather: null argument");
+  V_ARG(B > 0 && H > 0 && W > 0 && C > 0 && H % 2 == 0 && W % 2 == 0 && C % 8 == 0,
+        "pdm_vae_down_gather: needs even H and W and C % 8 == 0");
+  V_ARG((long long)B * (H / 2) * (W / 2) * 9 * (C / 8) <= 0x7fffffffLL * 256, "pdm_vae_down_gather: too many elements");
+  V_ARG(pdm::al16(x) && pdm::al16(A), "pdm_vae_down_gather: x and A must be 16-byte aligned");
+  D_HIP(pdm::down_gather_launch(x, (bf16*)A, B, H, W, C, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_vae_enc_tail(const void* g, int B, int H, int W, int C, const void* w, const float* cbias, const float* qw,
+                     const float* qb, float* moments, void* stream) {
+  V_ARG(g && w && cbias && qw && qb && moments, "pdm_vae_enc_tail: null argument");
+  V_ARG(B > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0, "pdm_vae_enc_tail: needs C % 32 == 0");
+  V_ARG((long long)B * H * W <= 0x7fffffffLL * 16, "pdm_vae_enc_tail: too many pixels");
+  V_ARG(pdm::al16(g) && pdm::al16(w), "pdm_vae_enc_tail: g and w must be 16-byte aligned");
+  D_HIP(pdm::enc_tail_launch((const bf16*)g, B, H, W, C, (const bf16*)w, cbias, qw, qb, moments, (hipStream_t)stream));
   return PDM_OK;
 }
 

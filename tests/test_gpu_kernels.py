@@ -164,7 +164,19 @@ def test_gemm_rows_split_past_2gib(lib):
     for b in (0, 8, 16):
         part = lib.gemm_conv3x3(x[b:b + 1].contiguous(), w, bias, lib.EPI_BF16).view(512 * 512, 128)
         assert torch.equal(full[b], part)
-    del x, full
+    # ... and with the GroupNorm partials of the output (this shape is fusable: N = 128 on the 512-row tile): the second
+    # part's partials land behind the first part's images (gemm_launch offsets gn_part by whole images)
+    per = lib.gn_part_elems(1, 512 * 512)
+    gp = torch.full((17 * per + 64,), float("nan"), dtype=torch.float64, device="cuda")
+    full_gn, fused = lib.gemm_conv3x3_gn(x, w, bias, lib.EPI_BF16, gp)
+    assert fused == 1 and torch.equal(full_gn.view(17, 512 * 512, 128), full)
+    assert not torch.isnan(gp[:17 * per]).any() and torch.isnan(gp[17 * per:]).all()
+    for b in (0, 8, 16):
+        gp1 = torch.full((per,), float("nan"), dtype=torch.float64, device="cuda")
+        part, fused = lib.gemm_conv3x3_gn(x[b:b + 1].contiguous(), w, bias, lib.EPI_BF16, gp1)
+        assert torch.equal(full[b], part.view(512 * 512, 128))
+        assert fused == 1 and torch.equal(gp[b * per:(b + 1) * per], gp1)
+    del x, full, full_gn
     # plain GEMM: 1.1 M rows x K = 1024 bf16 (2.25 GB)
     M, K, N = 1100 * 1024, 1024, 256
     a = torch.randn(M, K, device="cuda", generator=g).bfloat16()
