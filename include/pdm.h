@@ -518,6 +518,86 @@ int pdm_layernorm_backward(const float* x, const void* dh, int dh_bf16, const fl
                            float* dgamma, float* dbeta, int rows, int D, int accumulate, float* scratch,
                            size_t scratch_bytes, void* stream);
 
+/* ---- the training step's other kernels on their own (exposed for parity tests) ----------------------------------
+ * Caller-owned tensors, no trainer handle; each entry runs the launch code the trainer runs and returns PDM_ERR_ARG,
+ * before any launch, for a shape, stride, alignment or scratch size its kernel cannot take.  A row gather
+ * (rpg, gs, off) maps logical row r to row (r / rpg) * gs + off + r % rpg; rpg 0 = contiguous rows. */
+/* pdm_wgrad with the row gathers of A and B and the fused bias gradient: bias_out[n] (=, or += with bias_acc)
+ * sum_m A[m][n] (fp32 [N], 16-byte aligned, N % 4 == 0; NULL: none).  Gathered-over rows are never read. */
+int pdm_wgrad_gather(const void* A, int lda, int a_rpg, int a_gs, int a_off, const void* B, int ldb, int b_rpg, int b_gs,
+                     int b_off, float* C, int ldc, int M, int N, int K, int accumulate, float* bias_out, int bias_acc,
+                     float* scratch, size_t scratch_bytes, void* stream);
+/* dst[c] (=, or += with accumulate) sum_r x[gather(r)][c], c < ncols: x fp32 or bf16 (x_bf16) [.][ld], ncols % 4 == 0,
+ * ld % 4 == 0.  scratch (may be NULL / 0; a multiple of 32 bytes) holds the two halves the passes of <= 16 rows per
+ * chunk alternate between; too small a scratch means fewer, longer chunks, none a single pass. */
+int pdm_colsum(const void* x, int x_bf16, int ld, int rows, int ncols, int rpg, int gs, int off, float* dst,
+               int accumulate, float* scratch, size_t scratch_bytes, void* stream);
+/* pdm_layernorm_backward in its general form: x [.][ldx] and dx / dxb [.][lddx] at the gathered rows, dh [rows][lddh]
+ * not gathered; dgamma / dbeta = or += (accumulate_params); one column-sum chain covers both when dbeta == dgamma + D.
+ * D % 4 == 0, D <= 2048; scratch >= 40 D bytes (one block of partials), a multiple of 32. */
+int pdm_layernorm_backward_rows(const float* x, int ldx, const void* dh, int dh_bf16, int lddh, const float* gamma,
+                                float* dx, int lddx, void* dxb, float* dgamma, float* dbeta, int rows, int D, int rpg,
+                                int gs, int off, float eps, int accumulate, int accumulate_params, float* scratch,
+                                size_t scratch_bytes, void* stream);
+/* pdm_layernorm over gathered input rows: y[r] (bf16 [rows][ldy]) = LayerNorm(x[(r / rows_per_group) * group_stride +
+ * row_offset + r % rows_per_group]); rows_per_group > 0 (= rows: contiguous) */
+int pdm_layernorm_rows(const float* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int rows, int D,
+                       int rows_per_group, int group_stride, int row_offset, float eps, void* stream);
+/* exact-erf GELU (nn.GELU, libs/timm.py:102) on bf16: g = gelu(u); dg <- dg * gelu'(u) in place.  n % 8 == 0 */
+int pdm_gelu_forward(const void* u, void* g, long long n, void* stream);
+int pdm_gelu_backward(void* dg, const void* u, long long n, void* stream);
+/* LSimple (sde.py:270-279): loss[b] = mean over `per` elements of (target - pred)^2 and dpred = d(gscale * sum_b
+ * loss[b]) / d pred, fp32 [B][per]; tanh_bwd: pred = tanh(u) and dpred is the gradient w.r.t. u */
+int pdm_lsimple(const float* pred, const float* target, float* loss, float* dpred, int B, int per, float gscale,
+                int tanh_bwd, void* stream);
+/* backward of final_layer = nn.Conv2d(C, C, 3, padding=1) (libs/uvit.py:183), NCHW fp32: din, dw [C][C][3][3] and
+ * db [C] (all written) from the output gradient dout, the input `in` and the weight w */
+int pdm_conv3x3_backward(const float* dout, const float* in, const float* w, float* din, float* dw, float* db, int B,
+                         int C, int H, int W, void* stream);
+/* decoder_pred + unpatchify (libs/uvit.py:182,225-228,46-51).  Forward: token (b, i) = bf16 row b * in_group_stride +
+ * in_row_offset + i of x [.][ldx], W bf16 [P_pad][D] (rows >= P = p*p*C zero), bias fp32 [P] -> out fp32
+ * [B, C, Himg, Wimg] (tanh applied with act_tanh); D % 8 == 0, P_pad % 16 == 0, P_pad <= 64.  Backward: dpre fp32
+ * [B, C, Himg, Wimg], W fp32 [P][D] -> dtok bf16 [B*N][P_pad] (the gathered gradient, zero padded) and dx fp32
+ * [B*N][D] = dtok W */
+int pdm_head_forward(const void* x, int ldx, int in_group_stride, int in_row_offset, const void* W, const float* bias,
+                     float* out, int B, int D, int C, int p, int Himg, int Wimg, int P_pad, int act_tanh,
+                     void* stream);
+int pdm_head_backward(const float* dpre, const float* W, void* dtok, float* dx, int B, int D, int C, int p, int Himg,
+                      int Wimg, int P_pad, void* stream);
+/* token assembly (libs/uvit.py:201-212, libs/uvit_t2i.py:382-409): out[b][row] fp32 [B][L_total][ld_out] for the rows
+ * [label?][time?][context x n_ctx?][patches] + pos.  A row index of -1 leaves that kind of row out; the time row is
+ * time_emb[b] when given, else the sinusoidal embedding of t[b]; C*p*p <= 64. */
+typedef struct pdm_assemble_args {
+  const float* img;        /* [B, C, Himg, Wimg] */
+  int C, Himg, Wimg, p;
+  const float* patch_w;    /* [D][C*p*p], columns (c, p1, p2) */
+  const float* patch_b;    /* [D] */
+  const float* t;          /* [B] or NULL */
+  const float* time_emb;   /* [B][D] or NULL */
+  const int64_t* y;        /* [B] or NULL */
+  const float* label_emb;  /* [num_classes][D] or NULL */
+  const float* ctx_tokens; /* [B][n_ctx][D] or NULL */
+  int n_ctx;
+  const float* pos;        /* [>= L_total][D] */
+  float* out;
+  int ld_out;
+  int B, D, L_total;
+  int row0_patch, time_row, label_row, ctx_row;
+} pdm_assemble_args;
+int pdm_assemble(const pdm_assemble_args* args, void* stream);
+/* PatchEmbed operand: img fp32 [B, C, H, W] -> pv bf16 [B*N][ldp], columns k = (c, p1, p2), zeros for k >= C*p*p */
+int pdm_patchify(const float* img, void* pv, int B, int C, int H, int W, int p, int ldp, void* stream);
+/* dlab[y[b]][d] += dx[b * L + row][d], d < D (atomic: labels may repeat; y is not range-checked on the device) */
+int pdm_label_scatter(const float* dx, int L, int row, int D, const int64_t* y, float* dlab, int B, void* stream);
+/* dst[gd(r)] (=, or += with accumulate) src[gs(r)] and dstb[gd(r)] = bf16(dst[gd(r)]) over rows of D fp32, D % 4 == 0,
+ * each side with its own row gather */
+int pdm_rows_add_cast(float* dst, void* dstb, int drpg, int dgs, int doff, const float* src, int srpg, int sgs, int soff,
+                      int rows, int D, int accumulate, void* stream);
+/* dx += add (add may be NULL), dxb = bf16(dx); n % 4 == 0 */
+int pdm_add_cast(float* dx, const float* add, void* dxb, long long n, void* stream);
+/* w fp32 [N][K] -> wt bf16 [K][N]; N % 4 == 0, K % 4 == 0 */
+int pdm_transpose_bf16(const float* w, void* wt, int N, int K, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

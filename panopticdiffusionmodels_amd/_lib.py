@@ -69,6 +69,18 @@ class PdmEmStepArgs(ctypes.Structure):
     ]
 
 
+class PdmAssembleArgs(ctypes.Structure):
+    _fields_ = [
+        ("img", ctypes.c_void_p), ("C", ctypes.c_int), ("Himg", ctypes.c_int), ("Wimg", ctypes.c_int),
+        ("p", ctypes.c_int), ("patch_w", ctypes.c_void_p), ("patch_b", ctypes.c_void_p), ("t", ctypes.c_void_p),
+        ("time_emb", ctypes.c_void_p), ("y", ctypes.c_void_p), ("label_emb", ctypes.c_void_p),
+        ("ctx_tokens", ctypes.c_void_p), ("n_ctx", ctypes.c_int), ("pos", ctypes.c_void_p), ("out", ctypes.c_void_p),
+        ("ld_out", ctypes.c_int), ("B", ctypes.c_int), ("D", ctypes.c_int), ("L_total", ctypes.c_int),
+        ("row0_patch", ctypes.c_int), ("time_row", ctypes.c_int), ("label_row", ctypes.c_int),
+        ("ctx_row", ctypes.c_int),
+    ]
+
+
 class PdmGemmArgs(ctypes.Structure):
     _fields_ = [
         ("A1", ctypes.c_void_p), ("lda1", ctypes.c_int), ("A2", ctypes.c_void_p), ("lda2", ctypes.c_int),
@@ -254,6 +266,38 @@ _SIGS = {
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                               ctypes.c_size_t, ctypes.c_void_p]),
+    # the training step's other kernels on their own (include/pdm.h, parity tests)
+    "pdm_wgrad_gather": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p] + [ctypes.c_int] * 4 +
+                         [ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                                   ctypes.c_size_t, ctypes.c_void_p]),
+    "pdm_colsum": (ctypes.c_int, [ctypes.c_void_p] + [ctypes.c_int] * 7 + [ctypes.c_void_p, ctypes.c_int,
+                                                                           ctypes.c_void_p, ctypes.c_size_t,
+                                                                           ctypes.c_void_p]),
+    "pdm_layernorm_backward_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p] +
+                                    [ctypes.c_int] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                          ctypes.c_size_t, ctypes.c_void_p]),
+    "pdm_layernorm_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_float, ctypes.c_void_p]),
+    "pdm_gelu_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
+    "pdm_gelu_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p]),
+    "pdm_lsimple": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int,
+                                                           ctypes.c_void_p]),
+    "pdm_conv3x3_backward": (ctypes.c_int, [ctypes.c_void_p] * 6 + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
+    "pdm_head_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                        ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 8 + [ctypes.c_void_p]),
+    "pdm_head_backward": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 7 + [ctypes.c_void_p]),
+    "pdm_assemble": (ctypes.c_int, [ctypes.POINTER(PdmAssembleArgs), ctypes.c_void_p]),
+    "pdm_patchify": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
+    "pdm_label_scatter": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    "pdm_rows_add_cast": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 3 + [ctypes.c_void_p] +
+                          [ctypes.c_int] * 6 + [ctypes.c_void_p]),
+    "pdm_add_cast": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+                                    ctypes.c_void_p]),
+    "pdm_transpose_bf16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGS)
@@ -838,6 +882,137 @@ def layernorm_backward(x, dh, gamma, dx=None, accumulate=False):
                                      ptr(dg), ptr(db), rows, D, int(accumulate), ptr(scratch), scratch.numel() * 4,
                                      stream_ptr(x.device)), "pdm_layernorm_backward")
     return dx, dxb, dg, db
+
+
+# ---- the training step's other kernels on their own (include/pdm.h, parity tests) ------------------------------
+# The caller owns every tensor, outputs included (tests pre-fill them with sentinels); a gather is (rpg, gs, off).
+
+def _nbytes(t):
+    return t.numel() * t.element_size() if t is not None else 0
+
+
+def wgrad_gather(a, lda, b, ldb, c, ldc, M, N, K, a_gather=(0, 0, 0), b_gather=(0, 0, 0), accumulate=False,
+                 bias_out=None, bias_acc=False, scratch=None):
+    """pdm_wgrad_gather: c[n][k] (+)= sum_m a[ga(m)][n] b[gb(m)][k], bias_out[n] (+)= sum_m a[ga(m)][n]."""
+    require_gpu(a)
+    check(load().pdm_wgrad_gather(ptr(a), lda, int(a_gather[0]), int(a_gather[1]), int(a_gather[2]), ptr(b), ldb,
+                                  int(b_gather[0]), int(b_gather[1]), int(b_gather[2]), ptr(c), ldc, M, N, K,
+                                  int(accumulate), ptr(bias_out), int(bias_acc), ptr(scratch), _nbytes(scratch),
+                                  stream_ptr(a.device)), "pdm_wgrad_gather")
+
+
+def colsum(x, ld, rows, ncols, dst, gather=(0, 0, 0), accumulate=False, scratch=None):
+    """pdm_colsum: dst[c] (+)= sum_r x[gather(r)][c] of fp32 / bf16 x."""
+    require_gpu(x)
+    check(load().pdm_colsum(ptr(x), int(x.dtype == torch.bfloat16), ld, rows, ncols, int(gather[0]), int(gather[1]),
+                            int(gather[2]), ptr(dst), int(accumulate), ptr(scratch), _nbytes(scratch),
+                            stream_ptr(x.device)), "pdm_colsum")
+
+
+def layernorm_backward_rows(x, ldx, dh, lddh, gamma, dx, lddx, dxb, dgamma, dbeta, rows, D, scratch, gather=(0, 0, 0),
+                            eps=1e-5, accumulate=False, accumulate_params=False):
+    """pdm_layernorm_backward_rows (the general form of layernorm_backward)."""
+    require_gpu(x)
+    check(load().pdm_layernorm_backward_rows(ptr(x), ldx, ptr(dh), int(dh.dtype == torch.bfloat16), lddh, ptr(gamma),
+                                             ptr(dx), lddx, ptr(dxb), ptr(dgamma), ptr(dbeta), rows, D, int(gather[0]),
+                                             int(gather[1]), int(gather[2]), eps, int(accumulate),
+                                             int(accumulate_params), ptr(scratch), _nbytes(scratch),
+                                             stream_ptr(x.device)), "pdm_layernorm_backward_rows")
+
+
+def layernorm_rows(x, ldx, gamma, beta, y, ldy, rows, D, gather, eps=1e-5):
+    """pdm_layernorm_rows: y[r] = LayerNorm(x[gather(r)]) (bf16); gather = (rows_per_group > 0, group_stride, offset)."""
+    require_gpu(x)
+    check(load().pdm_layernorm_rows(ptr(x), ldx, ptr(gamma), ptr(beta), ptr(y), ldy, rows, D, int(gather[0]),
+                                    int(gather[1]), int(gather[2]), eps, stream_ptr(x.device)), "pdm_layernorm_rows")
+
+
+def gelu_forward(u, g, n=None):
+    require_gpu(u)
+    check(load().pdm_gelu_forward(ptr(u), ptr(g), u.numel() if n is None else n, stream_ptr(u.device)),
+          "pdm_gelu_forward")
+
+
+def gelu_backward(dg, u, n=None):
+    require_gpu(u)
+    check(load().pdm_gelu_backward(ptr(dg), ptr(u), u.numel() if n is None else n, stream_ptr(u.device)),
+          "pdm_gelu_backward")
+
+
+def lsimple(pred, target, loss, dpred, B, per, gscale, tanh_bwd=False):
+    require_gpu(pred)
+    check(load().pdm_lsimple(ptr(pred), ptr(target), ptr(loss), ptr(dpred), B, per, float(gscale), int(tanh_bwd),
+                             stream_ptr(pred.device)), "pdm_lsimple")
+
+
+def conv3x3_backward(dout, x, w, din, dw, db):
+    """pdm_conv3x3_backward of nn.Conv2d(C, C, 3, padding=1): dout, x [B, C, H, W], w [C, C, 3, 3]."""
+    require_gpu(dout)
+    B, C, H, W = dout.shape
+    check(load().pdm_conv3x3_backward(ptr(dout), ptr(x), ptr(w), ptr(din), ptr(dw), ptr(db), B, C, H, W,
+                                      stream_ptr(dout.device)), "pdm_conv3x3_backward")
+
+
+def head_forward(x, ldx, group_stride, row_offset, w, bias, out, B, D, C, p, H, W, P_pad, act_tanh=False):
+    require_gpu(x)
+    check(load().pdm_head_forward(ptr(x), ldx, group_stride, row_offset, ptr(w), ptr(bias), ptr(out), B, D, C, p, H, W,
+                                  P_pad, int(act_tanh), stream_ptr(x.device)), "pdm_head_forward")
+
+
+def head_backward(dpre, w, dtok, dx, B, D, C, p, H, W, P_pad):
+    require_gpu(dpre)
+    check(load().pdm_head_backward(ptr(dpre), ptr(w), ptr(dtok), ptr(dx), B, D, C, p, H, W, P_pad,
+                                   stream_ptr(dpre.device)), "pdm_head_backward")
+
+
+def assemble(img, p, patch_w, patch_b, pos, out, ld_out, D, L_total, row0_patch, t=None, time_emb=None, time_row=-1,
+             y=None, label_emb=None, label_row=-1, ctx_tokens=None, ctx_row=-1):
+    """pdm_assemble: token assembly of img [B, C, H, W] into out [B][L_total][ld_out]."""
+    require_gpu(img)
+    a = PdmAssembleArgs()
+    a.img = img.data_ptr()
+    a.B, a.C, a.Himg, a.Wimg = img.shape
+    a.p = p
+    a.patch_w, a.patch_b, a.pos, a.out = patch_w.data_ptr(), patch_b.data_ptr(), pos.data_ptr(), out.data_ptr()
+    a.t = t.data_ptr() if t is not None else None
+    a.time_emb = time_emb.data_ptr() if time_emb is not None else None
+    a.y = y.data_ptr() if y is not None else None
+    a.label_emb = label_emb.data_ptr() if label_emb is not None else None
+    a.ctx_tokens = ctx_tokens.data_ptr() if ctx_tokens is not None else None
+    a.n_ctx = ctx_tokens.shape[1] if ctx_tokens is not None else 0
+    a.ld_out, a.D, a.L_total = ld_out, D, L_total
+    a.row0_patch, a.time_row, a.label_row, a.ctx_row = row0_patch, time_row, label_row, ctx_row
+    check(load().pdm_assemble(ctypes.byref(a), stream_ptr(img.device)), "pdm_assemble")
+
+
+def patchify(img, pv, p, ldp):
+    require_gpu(img)
+    B, C, H, W = img.shape
+    check(load().pdm_patchify(ptr(img), ptr(pv), B, C, H, W, p, ldp, stream_ptr(img.device)), "pdm_patchify")
+
+
+def label_scatter(dx, L, row, D, y, dlab, B):
+    require_gpu(dx)
+    check(load().pdm_label_scatter(ptr(dx), L, row, D, ptr(y), ptr(dlab), B, stream_ptr(dx.device)),
+          "pdm_label_scatter")
+
+
+def rows_add_cast(dst, dstb, dst_gather, src, src_gather, rows, D, accumulate=False):
+    require_gpu(dst)
+    check(load().pdm_rows_add_cast(ptr(dst), ptr(dstb), int(dst_gather[0]), int(dst_gather[1]), int(dst_gather[2]),
+                                   ptr(src), int(src_gather[0]), int(src_gather[1]), int(src_gather[2]), rows, D,
+                                   int(accumulate), stream_ptr(dst.device)), "pdm_rows_add_cast")
+
+
+def add_cast(dx, add, dxb, n=None):
+    require_gpu(dx)
+    check(load().pdm_add_cast(ptr(dx), ptr(add), ptr(dxb), dx.numel() if n is None else n, stream_ptr(dx.device)),
+          "pdm_add_cast")
+
+
+def transpose_bf16(w, wt, N, K):
+    require_gpu(w)
+    check(load().pdm_transpose_bf16(ptr(w), ptr(wt), N, K, stream_ptr(w.device)), "pdm_transpose_bf16")
 
 
 class GemmProfiler:

@@ -881,4 +881,216 @@ int pdm_layernorm_backward(const float* x, const void* dh, int dh_bf16, const fl
   return PDM_OK;
 }
 
+
+// ---- every other training kernel on caller-owned tensors (parity tests, include/pdm.h) ----
+// Each entry fills the argument struct the trainer fills, checks what the kernel cannot take (PDM_ERR_ARG before any
+// launch) and calls the launch function the trainer calls.
+#define TK_ARG(cond, msg)                                          \
+  do {                                                             \
+    if (!(cond)) return pdm::set_error(PDM_ERR_ARG, msg);          \
+  } while (0)
+#define TK_AL(ptr, n) ((((uintptr_t)(ptr)) & ((n) - 1)) == 0)
+
+int pdm_wgrad_gather(const void* A, int lda, int a_rpg, int a_gs, int a_off, const void* B, int ldb, int b_rpg, int b_gs,
+                     int b_off, float* C, int ldc, int M, int N, int K, int accumulate, float* bias_out, int bias_acc,
+                     float* scratch, size_t scratch_bytes, void* stream) {
+  TK_ARG(A && B && C, "pdm_wgrad_gather: null operand");
+  TK_ARG(a_rpg >= 0 && a_gs >= 0 && a_off >= 0 && b_rpg >= 0 && b_gs >= 0 && b_off >= 0,
+         "pdm_wgrad_gather: negative row gather");
+  TK_ARG(lda >= N && ldb >= K && ldc >= K, "pdm_wgrad_gather: row strides must cover N / K");
+  TK_ARG(TK_AL(bias_out, 16) && TK_AL(scratch, 16), "pdm_wgrad_gather: bias_out / scratch must be 16-byte aligned");
+  TK_ARG(scratch || !scratch_bytes, "pdm_wgrad_gather: scratch_bytes without scratch");
+  pdm::WgradArgs a{};
+  a.A = static_cast<const bf16*>(A); a.lda = lda; a.a_rpg = a_rpg; a.a_gs = a_gs; a.a_off = a_off;
+  a.B = static_cast<const bf16*>(B); a.ldb = ldb; a.b_rpg = b_rpg; a.b_gs = b_gs; a.b_off = b_off;
+  a.C = C; a.ldc = ldc; a.M = M; a.N = N; a.K = K; a.accumulate = accumulate;
+  a.bias_out = bias_out; a.bias_acc = bias_acc;
+  TR_CHECK(pdm::wgrad_check(a));
+  TR_HIP(pdm::wgrad_launch(a, scratch, scratch_bytes, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_colsum(const void* x, int x_bf16, int ld, int rows, int ncols, int rpg, int gs, int off, float* dst,
+               int accumulate, float* scratch, size_t scratch_bytes, void* stream) {
+  TK_ARG(x && dst, "pdm_colsum: null pointer");
+  TK_ARG(rows > 0 && ncols > 0 && ncols % 4 == 0 && ld % 4 == 0 && ld >= ncols,
+         "pdm_colsum: rows > 0, ncols and ld multiples of 4, ld >= ncols");
+  TK_ARG(rpg >= 0 && gs >= 0 && off >= 0, "pdm_colsum: negative row gather");
+  TK_ARG(TK_AL(x, x_bf16 ? 8 : 16) && TK_AL(dst, 16), "pdm_colsum: x / dst must be aligned to 4 elements");
+  TK_ARG((scratch || !scratch_bytes) && TK_AL(scratch, 16) && scratch_bytes % 32 == 0,
+         "pdm_colsum: scratch must be 16-byte aligned and a multiple of 32 bytes (two aligned halves)");
+  TR_HIP(pdm::colsum_launch(x, x_bf16, ld, rows, ncols, rpg, gs, off, dst, accumulate, scratch, scratch_bytes,
+                            (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_layernorm_backward_rows(const float* x, int ldx, const void* dh, int dh_bf16, int lddh, const float* gamma,
+                                float* dx, int lddx, void* dxb, float* dgamma, float* dbeta, int rows, int D, int rpg,
+                                int gs, int off, float eps, int accumulate, int accumulate_params, float* scratch,
+                                size_t scratch_bytes, void* stream) {
+  TK_ARG(x && dh && gamma && dx && dgamma && dbeta && scratch, "pdm_layernorm_backward_rows: null pointer");
+  TK_ARG(rows > 0 && D > 0 && D % 4 == 0 && D <= 2048,
+         "pdm_layernorm_backward_rows: rows > 0, D a multiple of 4 and <= 2048");
+  TK_ARG(ldx >= D && lddh >= D && lddx >= D && ldx % 4 == 0 && lddh % 4 == 0 && lddx % 4 == 0,
+         "pdm_layernorm_backward_rows: row strides must be multiples of 4 and >= D");
+  TK_ARG(rpg >= 0 && gs >= 0 && off >= 0, "pdm_layernorm_backward_rows: negative row gather");
+  TK_ARG(TK_AL(x, 16) && TK_AL(gamma, 16) && TK_AL(dx, 16) && TK_AL(dgamma, 16) && TK_AL(dbeta, 16) &&
+             TK_AL(dh, dh_bf16 ? 8 : 16) && TK_AL(dxb, 8) && TK_AL(scratch, 16),
+         "pdm_layernorm_backward_rows: pointers must be aligned to 4 elements");
+  // one block's [2][D] partials plus ln_bwd_launch's reserve of four more such rows: nblk = 1
+  TK_ARG(scratch_bytes >= (size_t)40 * D && scratch_bytes % 32 == 0,
+         "pdm_layernorm_backward_rows: scratch must hold >= 40 D bytes, in multiples of 32");
+  pdm::LnBwdArgs a{};
+  a.x = x; a.ldx = ldx; a.lddh = lddh; a.gamma = gamma;
+  a.dx = dx; a.lddx = lddx; a.dxb = static_cast<bf16*>(dxb);
+  a.rows = rows; a.D = D; a.rpg = rpg; a.gs = gs; a.off = off; a.eps = eps;
+  a.accumulate = accumulate; a.accumulate_params = accumulate_params;
+  a.part = scratch; a.part_bytes = scratch_bytes;
+  TR_HIP(pdm::ln_bwd_launch(a, dh, dh_bf16, dgamma, dbeta, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_layernorm_rows(const float* x, int ldx, const float* gamma, const float* beta, void* y, int ldy, int rows, int D,
+                       int rows_per_group, int group_stride, int row_offset, float eps, void* stream) {
+  TK_ARG(group_stride >= 0 && row_offset >= 0, "pdm_layernorm_rows: negative row gather");
+  TK_ARG(ldx >= D && ldy >= D, "pdm_layernorm_rows: row strides must be >= D");
+  TK_ARG(TK_AL(x, 16) && TK_AL(gamma, 16) && TK_AL(beta, 16) && TK_AL(y, 8),
+         "pdm_layernorm_rows: pointers must be aligned to 4 elements");
+  pdm::LayerNormArgs a{};
+  a.x = x; a.ldx = ldx; a.gamma = gamma; a.beta = beta;
+  a.y = static_cast<bf16*>(y); a.ldy = ldy; a.rows = rows; a.D = D;
+  a.rows_per_group = rows_per_group; a.group_stride = group_stride; a.row_offset = row_offset;
+  a.eps = eps;
+  TR_CHECK(pdm::layernorm_check(a));
+  TR_HIP(pdm::layernorm_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_gelu_forward(const void* u, void* g, long long n, void* stream) {
+  TK_ARG(u && g && n > 0 && n % 8 == 0, "pdm_gelu_forward: n must be a positive multiple of 8");
+  TK_ARG(TK_AL(u, 16) && TK_AL(g, 16), "pdm_gelu_forward: pointers must be 16-byte aligned");
+  TR_HIP(pdm::gelu_fwd_launch(static_cast<const bf16*>(u), static_cast<bf16*>(g), n, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_gelu_backward(void* dg, const void* u, long long n, void* stream) {
+  TK_ARG(u && dg && n > 0 && n % 8 == 0, "pdm_gelu_backward: n must be a positive multiple of 8");
+  TK_ARG(TK_AL(u, 16) && TK_AL(dg, 16), "pdm_gelu_backward: pointers must be 16-byte aligned");
+  TR_HIP(pdm::gelu_bwd_launch(static_cast<bf16*>(dg), static_cast<const bf16*>(u), n, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_lsimple(const float* pred, const float* target, float* loss, float* dpred, int B, int per, float gscale,
+                int tanh_bwd, void* stream) {
+  TK_ARG(pred && target && loss && dpred, "pdm_lsimple: null pointer");
+  TK_ARG(B > 0 && per > 0, "pdm_lsimple: B and per must be positive");
+  TR_HIP(pdm::lsimple_launch(pred, target, loss, dpred, B, per, gscale, (hipStream_t)stream, tanh_bwd ? 1 : 0));
+  return PDM_OK;
+}
+
+int pdm_conv3x3_backward(const float* dout, const float* in, const float* w, float* din, float* dw, float* db, int B,
+                         int C, int H, int W, void* stream) {
+  TK_ARG(dout && in && w && din && dw && db, "pdm_conv3x3_backward: null pointer");
+  TK_ARG(B > 0 && C > 0 && H > 0 && W > 0, "pdm_conv3x3_backward: B, C, H, W must be positive");
+  TK_ARG((long long)C * C * 9 + C < 0x7fffffffLL && (long long)B * C * H * W < 0x7fffffffLL,
+         "pdm_conv3x3_backward: tensor too large");
+  TR_HIP(pdm::conv3x3_bwd_launch(dout, in, w, din, dw, db, B, C, H, W, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_head_forward(const void* x, int ldx, int in_group_stride, int in_row_offset, const void* W, const float* bias,
+                     float* out, int B, int D, int C, int p, int Himg, int Wimg, int P_pad, int act_tanh,
+                     void* stream) {
+  TK_ARG(B > 0 && D > 0 && C > 0 && p > 0 && Himg > 0 && Wimg > 0, "pdm_head_forward: sizes must be positive");
+  TK_ARG(Himg % p == 0 && Wimg % p == 0, "pdm_head_forward: image size must be divisible by the patch size");
+  TK_ARG(ldx >= D && in_group_stride >= (Himg / p) * (Wimg / p) && in_row_offset >= 0,
+         "pdm_head_forward: ldx >= D, group stride >= tokens per image, offset >= 0");
+  TK_ARG(TK_AL(x, 16) && TK_AL(W, 16), "pdm_head_forward: x / W must be 16-byte aligned");
+  pdm::HeadArgs a{};
+  a.x = static_cast<const bf16*>(x); a.ldx = ldx; a.in_group_stride = in_group_stride; a.in_row_offset = in_row_offset;
+  a.W = static_cast<const bf16*>(W); a.bias = bias; a.out = out;
+  a.B = B; a.D = D; a.C = C; a.p = p; a.Himg = Himg; a.Wimg = Wimg; a.P = p * p * C; a.P_pad = P_pad;
+  a.act_tanh = act_tanh ? 1 : 0;
+  TR_CHECK(pdm::head_check(a));
+  TR_HIP(pdm::head_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_head_backward(const float* dpre, const float* W, void* dtok, float* dx, int B, int D, int C, int p, int Himg,
+                      int Wimg, int P_pad, void* stream) {
+  TK_ARG(dpre && W && dtok && dx, "pdm_head_backward: null pointer");
+  TK_ARG(B > 0 && D > 0 && C > 0 && p > 0 && Himg > 0 && Wimg > 0, "pdm_head_backward: sizes must be positive");
+  TK_ARG(Himg % p == 0 && Wimg % p == 0, "pdm_head_backward: image size must be divisible by the patch size");
+  TK_ARG(p * p * C <= 64 && P_pad >= p * p * C && P_pad <= 64, "pdm_head_backward: p*p*C <= P_pad <= 64");
+  pdm::HeadBwdArgs a{};
+  a.dpre = dpre; a.W = W; a.dtok = static_cast<bf16*>(dtok); a.dx = dx;
+  a.B = B; a.D = D; a.C = C; a.p = p; a.Himg = Himg; a.Wimg = Wimg; a.P = p * p * C; a.P_pad = P_pad;
+  TR_HIP(pdm::head_bwd_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_assemble(const pdm_assemble_args* q, void* stream) {
+  TK_ARG(q, "pdm_assemble: null argument");
+  TK_ARG(q->C > 0 && q->p > 0 && q->Himg > 0 && q->Wimg > 0 && q->L_total > 0 && q->ld_out >= q->D,
+         "pdm_assemble: sizes must be positive and ld_out >= D");
+  const int np = q->p > 0 ? (q->Himg / q->p) * (q->Wimg / q->p) : 0;
+  TK_ARG(q->row0_patch >= 0 && q->row0_patch + np <= q->L_total, "pdm_assemble: patch rows outside the sequence");
+  TK_ARG(q->time_row < q->L_total && q->label_row < q->L_total, "pdm_assemble: time / label row outside the sequence");
+  TK_ARG(q->ctx_row < 0 || (q->n_ctx > 0 && q->ctx_row + q->n_ctx <= q->L_total),
+         "pdm_assemble: context rows outside the sequence");
+  pdm::AssembleArgs a{};
+  a.img = q->img; a.C = q->C; a.Himg = q->Himg; a.Wimg = q->Wimg; a.p = q->p;
+  a.patch_w = q->patch_w; a.patch_b = q->patch_b;
+  a.t = q->t; a.time_emb = q->time_emb; a.y = q->y; a.label_emb = q->label_emb;
+  a.ctx_tokens = q->ctx_tokens; a.n_ctx = q->n_ctx; a.pos = q->pos;
+  a.out = q->out; a.ld_out = q->ld_out; a.B = q->B; a.D = q->D; a.L_total = q->L_total;
+  a.row0_patch = q->row0_patch; a.time_row = q->time_row; a.label_row = q->label_row; a.ctx_row = q->ctx_row;
+  TR_CHECK(pdm::assemble_check(a));
+  TR_HIP(pdm::assemble_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_patchify(const float* img, void* pv, int B, int C, int H, int W, int p, int ldp, void* stream) {
+  TK_ARG(img && pv, "pdm_patchify: null pointer");
+  TK_ARG(B > 0 && C > 0 && p > 0 && H > 0 && W > 0 && H % p == 0 && W % p == 0,
+         "pdm_patchify: sizes must be positive and the image divisible by the patch size");
+  TK_ARG(ldp >= C * p * p, "pdm_patchify: ldp must be >= C*p*p");
+  TR_HIP(pdm::patchify_launch(img, static_cast<bf16*>(pv), B, C, H, W, p, ldp, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_label_scatter(const float* dx, int L, int row, int D, const int64_t* y, float* dlab, int B, void* stream) {
+  TK_ARG(dx && y && dlab, "pdm_label_scatter: null pointer");
+  TK_ARG(B > 0 && D > 0 && L > 0 && row >= 0 && row < L, "pdm_label_scatter: B, D, L positive and 0 <= row < L");
+  TR_HIP(pdm::label_scatter_launch(dx, L, row, D, y, dlab, B, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_rows_add_cast(float* dst, void* dstb, int drpg, int dgs, int doff, const float* src, int srpg, int sgs, int soff,
+                      int rows, int D, int accumulate, void* stream) {
+  TK_ARG(dst && dstb && src, "pdm_rows_add_cast: null pointer");
+  TK_ARG(rows > 0 && D > 0 && D % 4 == 0, "pdm_rows_add_cast: rows > 0 and D a positive multiple of 4");
+  TK_ARG(drpg >= 0 && dgs >= 0 && doff >= 0 && srpg >= 0 && sgs >= 0 && soff >= 0,
+         "pdm_rows_add_cast: negative row gather");
+  TK_ARG(TK_AL(dst, 16) && TK_AL(src, 16) && TK_AL(dstb, 8), "pdm_rows_add_cast: pointers must be aligned to 4 elements");
+  TR_HIP(pdm::rows_add_cast_launch(dst, static_cast<bf16*>(dstb), drpg, dgs, doff, src, srpg, sgs, soff, rows, D,
+                                   accumulate, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_add_cast(float* dx, const float* add, void* dxb, long long n, void* stream) {
+  TK_ARG(dx && dxb && n > 0 && n % 4 == 0, "pdm_add_cast: n must be a positive multiple of 4");
+  TK_ARG(TK_AL(dx, 16) && TK_AL(add, 16) && TK_AL(dxb, 8), "pdm_add_cast: pointers must be aligned to 4 elements");
+  TR_HIP(pdm::add_cast_launch(dx, add, static_cast<bf16*>(dxb), n, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_transpose_bf16(const float* w, void* wt, int N, int K, void* stream) {
+  TK_ARG(w && wt, "pdm_transpose_bf16: null pointer");
+  TK_ARG(N > 0 && K > 0 && N % 4 == 0 && K % 4 == 0, "pdm_transpose_bf16: N and K must be positive multiples of 4");
+  TK_ARG(TK_AL(w, 16) && TK_AL(wt, 8), "pdm_transpose_bf16: pointers must be aligned to 4 elements");
+  TR_HIP(pdm::transpose_bf16_launch(w, static_cast<bf16*>(wt), N, K, (hipStream_t)stream));
+  return PDM_OK;
+}
+
 }  // extern "C"

@@ -927,6 +927,9 @@ hipError_t ln_bwd_launch(const LnBwdArgs& args, const void* dh, int dh_bf16, flo
   // one wave per row, 4 per block; up to 1024 blocks (16 waves per CU) so row latency (two wave-sum chains per row)
   // overlaps across waves; each wave's dgamma / dbeta partials are summed by colsum_launch afterwards
   int nblk = std::min(1024, (p.rows + 3) / 4);
+  // a scratch below one block's share (nblk = 1: 40 D bytes) is rejected here, not by the wrap-around of the unsigned
+  // subtraction below
+  if (p.rows <= 0 || p.D <= 0 || !p.part || p.part_bytes < (size_t)40 * p.D) return hipErrorInvalidValue;
   // partials [2][4 nblk][D] + at least [2][D] for the column-sum passes must fit the scratch
   if (((size_t)nblk * 4 + 1) * 2 * p.D * 4 > p.part_bytes)
     nblk = (int)((p.part_bytes / ((size_t)2 * p.D * 4) - 1) / 4);

@@ -70,7 +70,11 @@ def test_c_entry_call_sites_match_sigs():
 WRAPPERS = {n: getattr(_lib, n) for n in ("gemm", "rowstats", "gemm_ln", "mx_quantize_gpu", "gemm_ex", "gemm_pair",
                                           "gemm_conv3x3", "gemm_batched", "layernorm", "attention", "lincomb",
                                           "stage_epilogue", "wgrad", "attention_backward", "layernorm_backward",
-                                          "mx_quantize", "mx_dequantize", "mx_quantize_centred", "_gemm_args")}
+                                          "mx_quantize", "mx_dequantize", "mx_quantize_centred", "_gemm_args",
+                                          "wgrad_gather", "colsum", "layernorm_backward_rows", "layernorm_rows",
+                                          "gelu_forward", "gelu_backward", "lsimple", "conv3x3_backward",
+                                          "head_forward", "head_backward", "assemble", "patchify", "label_scatter",
+                                          "rows_add_cast", "add_cast", "transpose_bf16")}
 
 
 def test_wrapper_call_sites_bind():
@@ -169,6 +173,41 @@ def test_wrappers_marshal_against_fake_library(fake):
     _lib.wgrad(torch.randn(16, 8).to(bf), torch.randn(16, 4).to(bf), scratch_mb=1)
     _lib.attention_backward(qkv, torch.randn(34, 64).to(bf), torch.randn(34, 64).to(bf), 2, 17, 1)
     _lib.layernorm_backward(torch.randn(16, 64), torch.randn(16, 64), torch.ones(64))
+    # the training kernels on caller-owned tensors
+    f32 = torch.float32
+    scratch = torch.empty(4096)
+    _lib.wgrad_gather(torch.randn(40, 16).to(bf), 16, torch.randn(40, 8).to(bf), 8, torch.zeros(16, 8), 8, 32, 16, 8,
+                      a_gather=(16, 20, 2), b_gather=(16, 20, 2), accumulate=True, bias_out=torch.zeros(16),
+                      bias_acc=True, scratch=scratch)
+    _lib.colsum(torch.randn(20, 8).to(bf), 8, 16, 8, torch.zeros(8), gather=(8, 10, 1), accumulate=True)
+    _lib.colsum(torch.randn(20, 8), 8, 20, 8, torch.zeros(8), scratch=scratch)
+    dgb = torch.zeros(2 * 64)
+    _lib.layernorm_backward_rows(torch.randn(22, 72), 72, torch.randn(18, 64).to(bf), 64, torch.ones(64),
+                                 torch.zeros(22, 72), 72, torch.zeros(22, 72, dtype=bf), dgb, dgb[64:], 18, 64, scratch,
+                                 gather=(9, 11, 2), accumulate=True, accumulate_params=True)
+    _lib.layernorm_rows(torch.randn(22, 72), 72, torch.ones(64), torch.zeros(64), torch.zeros(18, 64, dtype=bf), 64, 18,
+                        64, (9, 11, 2))
+    u = torch.randn(64).to(bf)
+    _lib.gelu_forward(u, torch.empty_like(u))
+    _lib.gelu_backward(torch.ones(64, dtype=bf), u)
+    _lib.lsimple(torch.randn(3, 5), torch.randn(3, 5), torch.zeros(3), torch.zeros(3, 5), 3, 5, 1 / 3, tanh_bwd=True)
+    _lib.conv3x3_backward(torch.randn(2, 3, 5, 5), torch.randn(2, 3, 5, 5), torch.randn(3, 3, 3, 3),
+                          torch.zeros(2, 3, 5, 5), torch.zeros(3, 3, 3, 3), torch.zeros(3))
+    _lib.head_forward(torch.randn(30, 64).to(bf), 64, 10, 1, torch.zeros(16, 64, dtype=bf), torch.zeros(12),
+                      torch.zeros(3, 3, 6, 6), 3, 64, 3, 2, 6, 6, 16, act_tanh=True)
+    _lib.head_backward(torch.randn(3, 3, 6, 6), torch.randn(12, 64), torch.zeros(27, 16, dtype=bf), torch.zeros(27, 64),
+                       3, 64, 3, 2, 6, 6, 16)
+    _lib.assemble(torch.randn(2, 3, 4, 4), 2, torch.randn(64, 12), torch.randn(64), torch.randn(8, 64),
+                  torch.zeros(2, 8, 64), 64, 64, 8, 4, t=torch.ones(2), time_row=1, y=torch.zeros(2, dtype=torch.long),
+                  label_emb=torch.randn(5, 64), label_row=0, ctx_tokens=torch.randn(2, 2, 64), ctx_row=2)
+    _lib.assemble(torch.randn(2, 3, 4, 4), 2, torch.randn(64, 12), torch.randn(64), torch.randn(8, 64),
+                  torch.zeros(2, 8, 64), 64, 64, 8, 4, time_emb=torch.randn(2, 64), time_row=0)
+    _lib.patchify(torch.randn(2, 3, 4, 6), torch.zeros(12, 16, dtype=bf), 2, 16)
+    _lib.label_scatter(torch.randn(10, 64), 5, 0, 64, torch.zeros(2, dtype=torch.long), torch.zeros(4, 64), 2)
+    _lib.rows_add_cast(torch.zeros(20, 8, dtype=f32), torch.zeros(20, 8, dtype=bf), (4, 10, 3), torch.randn(8, 8),
+                       (0, 0, 0), 8, 8, accumulate=True)
+    _lib.add_cast(torch.zeros(16), None, torch.zeros(16, dtype=bf))
+    _lib.transpose_bf16(torch.randn(4, 8), torch.zeros(8, 4, dtype=bf), 4, 8)
 
     class _Native:
         lib, h = fake, ctypes.c_void_p(1)
@@ -179,7 +218,11 @@ def test_wrappers_marshal_against_fake_library(fake):
     for name in ("pdm_gemm_bf16", "pdm_rowstats", "pdm_gemm_bf16_ln", "pdm_mx_quantize", "pdm_gemm", "pdm_gemm_pair",
                  "pdm_gemm_conv3x3_bf16", "pdm_gemm_batched_bf16", "pdm_layernorm", "pdm_attention",
                  "pdm_attention_log2", "pdm_lincomb", "pdm_stage_epilogue", "pdm_wgrad", "pdm_attention_backward",
-                 "pdm_layernorm_backward", "pdm_uvit_profile", "pdm_uvit_profile_read"):
+                 "pdm_layernorm_backward", "pdm_uvit_profile", "pdm_uvit_profile_read", "pdm_wgrad_gather",
+                 "pdm_colsum", "pdm_layernorm_backward_rows", "pdm_layernorm_rows", "pdm_gelu_forward",
+                 "pdm_gelu_backward", "pdm_lsimple", "pdm_conv3x3_backward", "pdm_head_forward", "pdm_head_backward",
+                 "pdm_assemble", "pdm_patchify", "pdm_label_scatter", "pdm_rows_add_cast", "pdm_add_cast",
+                 "pdm_transpose_bf16"):
         assert name in fake.calls, name
 
 
