@@ -501,6 +501,24 @@ int pdm_train_step_t2i(pdm_trainer* t, const float* xt, const float* tvals, cons
  * ema = ema_rate * ema + (1 - ema_rate) * params (utils.ema; ema may be NULL) and the bf16 copies */
 int pdm_train_adamw(pdm_trainer* t, float* m, float* v, float* ema, const float* grads2, float lr, float beta1,
                     float beta2, float eps, float weight_decay, int step, float ema_rate, void* stream);
+/* element range [0, active) of the flat buffers that pdm_train_adamw updates: the parameters the forward uses.  A
+ * parameter whose offset is >= active (t2i: zero_convs.{even}, mask_embed_0) never gets a gradient, so it has no
+ * optimizer state, as torch.optim keeps none for a parameter without a gradient. */
+int pdm_train_active(const pdm_trainer* t, long long* active);
+/* utils.grad_norm / accelerator.clip_grad_norm_ (train.py:89-90) on the gradient buffer, between the all-reduce and
+ * pdm_train_adamw: out2[0] = L2 norm over [0, active) of the gradients (of grads + grads2 element by element when
+ * grads2 is not NULL), out2[1] = coef = min(max_norm / (norm + 1e-6), 1); with max_norm > 0 both buffers are then
+ * multiplied by coef in place (nothing is written when coef >= 1; a NaN norm scales by NaN, as torch does);
+ * max_norm <= 0: the norm only.  No host synchronisation and no float atomics: the same gradients give the same
+ * bits on every run and rank.  scratch: fp32 partials, PDM_GRAD_NORM_SCRATCH_BYTES is always enough.  PDM_ERR_ARG
+ * before any launch for a NULL / misaligned pointer (gradients 16 bytes, out2 / scratch 4) or too small a scratch. */
+#define PDM_GRAD_NORM_SCRATCH_BYTES 4096
+int pdm_train_grad_norm(pdm_trainer* t, float* grads2, float max_norm, float* out2, float* scratch,
+                        size_t scratch_bytes, void* stream);
+/* the same launch on caller-owned buffers of n > 0 floats (parity tests): g2 may be NULL; scratch >= one float per
+ * block of the first pass, min(ceil(floor(n / 4) / 256), 1024) blocks (at least one) */
+int pdm_grad_norm_clip(float* g, float* g2, long long n, float max_norm, float* out2, float* scratch,
+                       size_t scratch_bytes, void* stream);
 /* the backward kernels on their own (parity tests).  pdm_wgrad: C[n][k] (+)= sum_m A[m][n] B[m][k] (bf16 A [M][lda],
  * B [M][ldb], fp32 C [N][ldc]; scratch for split-reduction partials, may be NULL).  pdm_attention_backward: softmax
  * attention over packed qkv [B*L][3*H*Dh] with output o [B*L][H*Dh] and its gradient dout -> dqkv (Dh 64, L <= 608;

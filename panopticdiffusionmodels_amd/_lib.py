@@ -256,6 +256,11 @@ _SIGS = {
     "pdm_train_adamw": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                        ctypes.c_int, ctypes.c_float, ctypes.c_void_p]),
+    "pdm_train_active": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
+    "pdm_train_grad_norm": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    "pdm_grad_norm_clip": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_float,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "pdm_set_wgrad_tile": (ctypes.c_int, [ctypes.c_int]),
     "pdm_wgrad": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                  ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -943,6 +948,16 @@ def lsimple(pred, target, loss, dpred, B, per, gscale, tanh_bwd=False):
     require_gpu(pred)
     check(load().pdm_lsimple(ptr(pred), ptr(target), ptr(loss), ptr(dpred), B, per, float(gscale), int(tanh_bwd),
                              stream_ptr(pred.device)), "pdm_lsimple")
+
+
+GRAD_NORM_SCRATCH_BYTES = 4096   # PDM_GRAD_NORM_SCRATCH_BYTES: enough for any n
+
+
+def grad_norm_clip(g, g2, n, max_norm, out2, scratch):
+    """pdm_grad_norm_clip: out2 = {||g (+ g2)||, coef}; with max_norm > 0, g (and g2) *= coef in place if coef < 1."""
+    require_gpu(g)
+    check(load().pdm_grad_norm_clip(ptr(g), ptr(g2), int(n), float(max_norm), ptr(out2), ptr(scratch),
+                                    _nbytes(scratch), stream_ptr(g.device)), "pdm_grad_norm_clip")
 
 
 def conv3x3_backward(dout, x, w, din, dw, db):

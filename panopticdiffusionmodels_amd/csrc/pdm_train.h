@@ -102,4 +102,18 @@ struct AdamWArgs {
 };
 hipError_t adamw_launch(const AdamWArgs& a, long long n, hipStream_t stream);
 
+// out = {L2 norm of g (+ g2, element by element) over n floats, coef = min(max_norm / (norm + 1e-6), 1)}; with
+// max_norm > 0 both buffers are then multiplied by coef in place unless coef >= 1 (clip_grad_norm_); max_norm <= 0:
+// the norm only.  part: one float per block of the first pass (grad_norm_scratch_bytes).  Deterministic (no atomics).
+struct GradNormArgs {
+  float* g; float* g2; long long n;
+  float max_norm;
+  float* out; float* part;
+};
+constexpr int GRAD_NORM_MAX_BLOCKS = 1024;
+int grad_norm_blocks(long long n);
+size_t grad_norm_scratch_bytes(long long n);
+const char* grad_norm_check(const GradNormArgs& a, size_t scratch_bytes);
+hipError_t grad_norm_launch(const GradNormArgs& a, hipStream_t stream);
+
 }  // namespace pdm

@@ -837,6 +837,31 @@ int pdm_train_adamw(pdm_trainer* t, float* m, float* v, float* ema, const float*
   return refresh(t, s);
 }
 
+int pdm_train_active(const pdm_trainer* t, long long* active) {
+  if (!t || !active) return pdm::set_error(PDM_ERR_ARG, "pdm_train_active: null argument");
+  *active = t->active;
+  return PDM_OK;
+}
+
+int pdm_train_grad_norm(pdm_trainer* t, float* grads2, float max_norm, float* out2, float* scratch,
+                        size_t scratch_bytes, void* stream) {
+  if (!t || !t->Pm) return pdm::set_error(PDM_ERR_STATE, "pdm_train_grad_norm: buffers not set");
+  pdm::GradNormArgs a{};
+  a.g = t->G; a.g2 = grads2; a.n = t->active; a.max_norm = max_norm; a.out = out2; a.part = scratch;
+  TR_CHECK(pdm::grad_norm_check(a, scratch_bytes));
+  TR_HIP(pdm::grad_norm_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_grad_norm_clip(float* g, float* g2, long long n, float max_norm, float* out2, float* scratch,
+                       size_t scratch_bytes, void* stream) {
+  pdm::GradNormArgs a{};
+  a.g = g; a.g2 = g2; a.n = n; a.max_norm = max_norm; a.out = out2; a.part = scratch;
+  TR_CHECK(pdm::grad_norm_check(a, scratch_bytes));
+  TR_HIP(pdm::grad_norm_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
 int pdm_set_wgrad_tile(int tile) {
   if (tile != 0 && tile != 128 && tile != 256) return pdm::set_error(PDM_ERR_ARG, "pdm_set_wgrad_tile: 0, 128 or 256");
   pdm::g_wgrad_tile = tile;

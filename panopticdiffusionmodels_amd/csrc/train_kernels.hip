@@ -8,7 +8,8 @@
 //                      in HBM.  The long reduction (M = tokens) is split over workgroups into fp32 partials.
 //   * attn_bwd_kernel  softmax attention backward for one (sequence, head) per workgroup, Q K V dO resident in LDS
 //                      (L <= 288) or two of them at a time (L <= 608: the t2i image / mask streams)
-//   * LayerNorm / GELU / bias / embedding / final conv / decoder_pred backward, the LSimple loss, AdamW + EMA.
+//   * LayerNorm / GELU / bias / embedding / final conv / decoder_pred backward, the LSimple loss, AdamW + EMA,
+//     the global gradient norm and its clipping (train.py:89-90).
 #include <algorithm>
 
 #include "pdm_common.h"
@@ -822,6 +823,79 @@ __global__ __launch_bounds__(256) void adamw_kernel(AdamWArgs a, long long n) {
   }
 }
 
+// Global gradient norm (utils.grad_norm / torch.nn.utils.clip_grad_norm_) over the flat gradient buffer, of g + g2
+// element by element when a second lane's buffer is given (the quantity adamw_kernel consumes).  No float atomics:
+// every sum below has one fixed order for a given n, so the norm is the same bits from run to run and on every rank.
+//   grad_sumsq_kernel: per thread one f32x4 accumulator over 16-byte loads (grid stride; the n % 4 tail elements go
+//     to the first lanes of block 0), (a0 + a1) + (a2 + a3), xor-butterfly over the wave, the four waves' sums added
+//     in order by thread 0 -> part[block]
+//   grad_norm_final_kernel (one block): thread i sums part[i], part[i + 256], ... in order, the same wave / block
+//     reduction, then out = {sqrt(sum), coef}; coef = min(max_norm / (norm + 1e-6), 1), a NaN kept (torch.clamp),
+//     1 for max_norm <= 0 (norm only)
+//   grad_scale_kernel: every block returns before touching memory when coef >= 1; otherwise both buffers are
+//     multiplied in place (a NaN coef fails the test and scales by NaN, as torch does)
+__device__ __forceinline__ float block_sum_256(float s, float* red) {
+  s = wave_sum(s);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) red[wave] = s;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(GradNormArgs a, long long n4) {
+  __shared__ float red[4];
+  const f32x4* g = reinterpret_cast<const f32x4*>(a.g);
+  const f32x4* g2 = reinterpret_cast<const f32x4*>(a.g2);
+  f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n4; e += (long long)gridDim.x * 256) {
+    f32x4 v = g[e];
+    if (g2) v += g2[e];
+    acc += v * v;
+  }
+  float s = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+  if (blockIdx.x == 0 && (long long)threadIdx.x < a.n - n4 * 4) {
+    const long long e = n4 * 4 + threadIdx.x;
+    const float v = a.g2 ? a.g[e] + a.g2[e] : a.g[e];
+    s += v * v;
+  }
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) a.part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void grad_norm_final_kernel(GradNormArgs a, int nparts) {
+  __shared__ float red[4];
+  float s = 0.f;
+  for (int i = threadIdx.x; i < nparts; i += 256) s += a.part[i];
+  s = block_sum_256(s, red);
+  if (threadIdx.x == 0) {
+    const float norm = sqrtf(s);
+    float coef = 1.0f;
+    if (a.max_norm > 0.f) {
+      const float c = a.max_norm / (norm + 1e-6f);
+      coef = c >= 1.0f ? 1.0f : c;
+    }
+    a.out[0] = norm;
+    a.out[1] = coef;
+  }
+}
+
+__global__ __launch_bounds__(256) void grad_scale_kernel(GradNormArgs a, long long n4) {
+  const float c = a.out[1];
+  if (c >= 1.0f) return;
+  f32x4* g = reinterpret_cast<f32x4*>(a.g);
+  f32x4* g2 = reinterpret_cast<f32x4*>(a.g2);
+  for (long long e = blockIdx.x * 256ll + threadIdx.x; e < n4; e += (long long)gridDim.x * 256) {
+    g[e] = g[e] * c;
+    if (g2) g2[e] = g2[e] * c;
+  }
+  if (blockIdx.x == 0 && (long long)threadIdx.x < a.n - n4 * 4) {
+    const long long e = n4 * 4 + threadIdx.x;
+    a.g[e] = a.g[e] * c;
+    if (a.g2) a.g2[e] = a.g2[e] * c;
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1060,6 +1134,32 @@ hipError_t transpose_bf16_launch(const float* w, bf16* wt, int N, int K, hipStre
 
 hipError_t adamw_launch(const AdamWArgs& a, long long n, hipStream_t stream) {
   hipLaunchKernelGGL(adamw_kernel, dim3(grid_for(n)), dim3(256), 0, stream, a, n);
+  return hipGetLastError();
+}
+
+// one block per 256 f32x4 up to GRAD_NORM_MAX_BLOCKS (16 waves on each of the 256 CUs), grid stride beyond
+int grad_norm_blocks(long long n) {
+  const long long b = (n / 4 + 255) / 256;
+  return (int)(b < 1 ? 1 : (b > GRAD_NORM_MAX_BLOCKS ? GRAD_NORM_MAX_BLOCKS : b));
+}
+
+size_t grad_norm_scratch_bytes(long long n) { return (size_t)grad_norm_blocks(n) * sizeof(float); }
+
+const char* grad_norm_check(const GradNormArgs& a, size_t scratch_bytes) {
+  if (!a.g || !a.out || !a.part) return "grad_norm: null gradient, output or scratch pointer";
+  if (a.n <= 0) return "grad_norm: n must be positive";
+  if (((uintptr_t)a.g | (uintptr_t)a.g2) & 15) return "grad_norm: gradient buffers must be 16-byte aligned";
+  if (((uintptr_t)a.out | (uintptr_t)a.part) & 3) return "grad_norm: output / scratch must be 4-byte aligned";
+  if (scratch_bytes < grad_norm_scratch_bytes(a.n)) return "grad_norm: scratch below one float per block";
+  return nullptr;
+}
+
+hipError_t grad_norm_launch(const GradNormArgs& a, hipStream_t stream) {
+  const int blocks = grad_norm_blocks(a.n);
+  const long long n4 = a.n / 4;
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3(blocks), dim3(256), 0, stream, a, n4);
+  hipLaunchKernelGGL(grad_norm_final_kernel, dim3(1), dim3(256), 0, stream, a, blocks);
+  if (a.max_norm > 0.f) hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks), dim3(256), 0, stream, a, n4);
   return hipGetLastError();
 }
 

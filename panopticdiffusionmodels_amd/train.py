@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, checkpoint
 from .native import cfg_struct
 from .sde import VPSDE, mos, stp
 
@@ -84,7 +84,8 @@ class HipTrainState:
     """Parameters, gradients, AdamW moments and the EMA copy of one U-ViT in flat device buffers (pdm_train_*).
 
     `state_dict()` / `ema_state_dict()` hand back reference-keyed tensors (views copied out), so checkpoints
-    interoperate with utils.TrainState's nnet / nnet_ema files."""
+    interoperate with utils.TrainState's nnet / nnet_ema files; `save` / `load` / `resume` read and write the
+    reference's whole checkpoint directory (checkpoint.py), optimizer and scheduler state included."""
 
     def __init__(self, nnet_kwargs, device="cuda", optimizer=None, lr_scheduler=None, ema_rate=0.9999, lanes=1):
         """lanes=2 splits each batch into two halves run concurrently on their own streams (a second pdm_train
@@ -338,17 +339,154 @@ class HipTrainState:
         """The rate the next optimizer_step applies (optimizer.param_groups[0]['lr'] after lr_scheduler.step())."""
         return customized_lr(self.optimizer["lr"], self.step, self.lr_scheduler.get("warmup_steps", -1))
 
+    # ---- gradient norm / clipping (train.py:89-90, utils.grad_norm) --------------------------------------------
+    def _grad_norm(self, max_norm):
+        """pdm_train_grad_norm on the current stream: {norm, coef} into two device floats, the gradient buffers
+        scaled in place when max_norm > 0 and coef < 1.  Returns the norm (a copy: the next call overwrites it)."""
+        if getattr(self, "_gn", None) is None:
+            self._gn = torch.zeros(2, dtype=torch.float32, device=self.device)
+            self._gn_scratch = torch.empty(_lib.GRAD_NORM_SCRATCH_BYTES // 4, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.pdm_train_grad_norm(self.h, _lib.ptr(self.G2), float(max_norm), _lib.ptr(self._gn),
+                                                _lib.ptr(self._gn_scratch), _lib.GRAD_NORM_SCRATCH_BYTES,
+                                                _lib.stream_ptr(self.device)), "pdm_train_grad_norm")
+        return self._gn[0].clone()
+
+    def grad_norm(self):
+        """utils.grad_norm (utils.py:643-649): the L2 norm over every parameter's gradient (both lanes summed), a 0-d
+        device tensor; no host synchronisation."""
+        return self._grad_norm(0.0)
+
+    def clip_grad_norm_(self, max_norm):
+        """torch.nn.utils.clip_grad_norm_ on the gradient buffer: gradients *= min(max_norm / (total_norm + 1e-6), 1)
+        in place (nothing is written when the factor is 1), decided on the device.  Returns the norm before
+        clipping."""
+        if not max_norm > 0:
+            raise ValueError(f"clip_grad_norm_: max_norm must be positive, got {max_norm}")
+        return self._grad_norm(max_norm)
+
+    # ---- checkpoints (utils.TrainState.save / load / resume, utils.py:367-405) ----------------------------------
+    def param_order(self):
+        """[(name, shape)] in the reference's nnet.parameters() order (the optimizer state's index)."""
+        return checkpoint.param_order(dict(self.kw, name="uvit_t2i" if self.t2i else "uvit"))
+
+    def stateless_params(self):
+        """Parameters outside the AdamW range [0, active): the forward never uses them (t2i: zero_convs.{even},
+        mask_embed_0), so they get no gradient and, as in torch, no optimizer state."""
+        active = ctypes.c_longlong()
+        _lib.check(self.lib.pdm_train_active(self.h, ctypes.byref(active)), "pdm_train_active")
+        return {k for k, (off, _) in self.index.items() if off >= active.value}
+
+    def _host_dict(self, flat, names=None):
+        """One device-to-host copy of a flat buffer, sliced on the host into reference-keyed tensors (own storage)."""
+        host = flat.detach().cpu()
+        order = self.param_order()
+        return {k: host[self.index[k][0]: self.index[k][0] + self.index[k][1]].reshape(shape).clone()
+                for k, shape in order if names is None or k in names}
+
+    def _hyper(self):
+        o = self.optimizer
+        return dict(lr=o["lr"], betas=tuple(o["betas"]), eps=o.get("eps", 1e-8), weight_decay=o["weight_decay"])
+
+    def optimizer_state_dict(self):
+        """A torch.optim.AdamW.state_dict() of the reference's optimizer at this step (CPU tensors)."""
+        order, stateless = self.param_order(), self.stateless_params()
+        used = {k for k, _ in order} - stateless
+        m = self._host_dict(self.M, used) if self.step > 0 else {}
+        v = self._host_dict(self.V, used) if self.step > 0 else {}
+        return checkpoint.optimizer_state_dict(order, m, v, self.step, self._hyper(),
+                                               self.lr_scheduler.get("warmup_steps", -1), stateless)
+
+    def lr_scheduler_state_dict(self):
+        """The LambdaLR.state_dict() of utils.customized_lr_scheduler at this step."""
+        return checkpoint.lr_scheduler_state_dict(self.step, self._hyper(), self.lr_scheduler.get("warmup_steps", -1))
+
+    def _put(self, flat, tensors, base=None):
+        """Reference-keyed CPU tensors -> a flat device buffer, through one host buffer and one copy."""
+        host = torch.zeros(self.n, dtype=torch.float32) if base is None else base.detach().cpu()
+        for k, v in tensors.items():
+            off, numel = self.index[k]
+            host[off: off + numel].copy_(v.detach().to("cpu", torch.float32).reshape(-1))
+        with torch.no_grad():
+            flat.copy_(host.to(self.device))
+
+    def load_optimizer_state_dict(self, sd):
+        """optimizer.load_state_dict of the reference: moments, the step counter and betas / eps / weight decay /
+        base LR from the file.  Returns the per-parameter step (None: no step taken)."""
+        m, v, step, hyper = checkpoint.read_optimizer_state_dict(sd, self.param_order(), self.stateless_params())
+        self._put(self.M, m)
+        self._put(self.V, v)
+        self.optimizer.update(hyper)
+        self.step = 0 if step is None else step
+        return step
+
+    def load_lr_scheduler_state_dict(self, sd):
+        """lr_scheduler.load_state_dict: the warm-up position (which must be the optimizer's step) and the base LR."""
+        last_epoch, base_lr = checkpoint.read_lr_scheduler_state_dict(sd)
+        if last_epoch != self.step:
+            raise ValueError(f"lr_scheduler last_epoch = {last_epoch}, optimizer step = {self.step} "
+                             f"(HipTrainState keeps one step counter)")
+        self.optimizer["lr"] = base_lr
+        return last_epoch
+
+    def save(self, path):
+        """utils.TrainState.save: step.pth, nnet.pth, nnet_ema.pth, optimizer.pth, lr_scheduler.pth under `path`,
+        each as torch writes it for the reference."""
+        checkpoint.write_dir(path, self.step, self._host_dict(self.P), self._host_dict(self.E),
+                             self.optimizer_state_dict(), self.lr_scheduler_state_dict())
+
+    def load(self, path, strict=True):
+        """utils.TrainState.load.  strict=False is the reference's load_state_dict(..., strict=False) for the two nets
+        (unknown keys ignored, missing ones keep their values).  Everything is checked before any state changes;
+        afterwards the bf16 copies are rebuilt and the gradient buffers are zero."""
+        step, nnet_sd, ema_sd, opt_sd, sched_sd = checkpoint.read_dir(path)
+        order, stateless = self.param_order(), self.stateless_params()
+        shapes = dict(order)
+        for what, sd in (("nnet", nnet_sd), ("nnet_ema", ema_sd)):
+            missing, extra = set(shapes) - set(sd), set(sd) - set(shapes)
+            if strict and (missing or extra):
+                raise KeyError(f"{what}.pth mismatch: missing {sorted(missing)[:5]}, unexpected {sorted(extra)[:5]}")
+            for k in set(sd) & set(shapes):
+                if tuple(sd[k].shape) != shapes[k]:
+                    raise ValueError(f"{what}.pth: {k} has shape {tuple(sd[k].shape)}, not {shapes[k]}")
+        m, v, pstep, hyper = checkpoint.read_optimizer_state_dict(opt_sd, order, stateless)
+        last_epoch, base_lr = checkpoint.read_lr_scheduler_state_dict(sched_sd)
+        step = checkpoint.check_steps(step, pstep, last_epoch)
+        self._put(self.P, {k: t for k, t in nnet_sd.items() if k in shapes}, base=self.P)
+        self._put(self.E, {k: t for k, t in ema_sd.items() if k in shapes}, base=self.E)
+        self._put(self.M, m)
+        self._put(self.V, v)
+        self.shapes.update(shapes)
+        self.optimizer.update(hyper)
+        self.optimizer["lr"] = base_lr
+        self.step = step
+        self.G.zero_()
+        if self.G2 is not None:
+            self.G2.zero_()
+        _lib.check(self.lib.pdm_train_refresh(self.h, _lib.stream_ptr(self.device)), "pdm_train_refresh")
+
+    def resume(self, ckpt_root, step=None):
+        """utils.TrainState.resume: load the newest <step>.ckpt (or best.ckpt, or the given step) under ckpt_root;
+        False when there is nothing to resume from."""
+        path = checkpoint.resume_path(ckpt_root, step)
+        if path is None:
+            return False
+        self.load(path)
+        return True
+
     def train_step(self, x0, y=None, objective="discrete", schedule=None, sde=None, rng=None, context=None,
-                   panoptic=None):
+                   panoptic=None, grad_clip=None):
         """One iteration of train_ldm_discrete.py:159-175 (objective 'discrete', Schedule) or train_ldm.py
         (objective 'sde', VPSDE + noise_pred); a t2i trainer runs train_t2i_discrete.py:446-478 on (x0, context,
-        panoptic integer masks).  Returns dict(loss=mean loss over the global batch, lr=...) (+ loss_mask)."""
+        panoptic integer masks).  grad_clip > 0 clips the global gradient norm between the all-reduce and the
+        optimizer (train.py:89-90).  Returns dict(loss=mean loss over the global batch, lr=...) (+ loss_mask)."""
         if self.t2i:
             schedule = schedule or Schedule(stable_diffusion_beta_schedule())
             scaled = int2bits(panoptic).to(x0.device) * 2.0 - 1.0
             n, eps, xn, eps_m, mask_n = schedule.sample(x0, rng, panoptic=scaled)
             loss, loss_m = self.forward_backward_t2i(xn, n.float(), context, mask_n, eps, scaled)
             self.all_reduce_grads()
+            if grad_clip is not None and grad_clip > 0:
+                self.clip_grad_norm_(grad_clip)
             self.optimizer_step()
             ms = torch.stack([loss.mean(), loss_m.mean()])
             if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -365,6 +503,8 @@ class HipTrainState:
         else:
             raise NotImplementedError(objective)
         self.all_reduce_grads()
+        if grad_clip is not None and grad_clip > 0:
+            self.clip_grad_norm_(grad_clip)
         self.optimizer_step()
         m = loss.mean()
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
@@ -373,6 +513,28 @@ class HipTrainState:
         # the reference returns optimizer.param_groups[0]['lr'] read after lr_scheduler.step()
         # (train_ldm_discrete.py:174-177): the rate of the NEXT step
         return dict(loss=m, lr=self.current_lr())
+
+
+def stateless_params(nnet_kwargs):
+    """The parameters of a network that the trainer keeps outside its AdamW range (pdm_train_active): those the
+    forward never uses, which get no optimizer state in a checkpoint.  Host logic only (no GPU)."""
+    kw = dict(nnet_kwargs)
+    t2i = kw.pop("name", "uvit") == "uvit_t2i"
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    _lib.check(lib.pdm_train_create(ctypes.byref(cfg_struct(kw, t2i)), ctypes.byref(h)), "pdm_train_create")
+    try:
+        active, off = ctypes.c_longlong(), ctypes.c_longlong()
+        _lib.check(lib.pdm_train_active(h, ctypes.byref(active)), "pdm_train_active")
+        buf = ctypes.create_string_buffer(256)
+        out = set()
+        for i in range(lib.pdm_train_param_count(h)):
+            _lib.check(lib.pdm_train_param_info(h, i, buf, 256, ctypes.byref(off), None))
+            if off.value >= active.value:
+                out.add(buf.value.decode())
+        return out
+    finally:
+        lib.pdm_train_destroy(h)
 
 
 def average_gradients(g):
@@ -400,4 +562,4 @@ def LSimple(x0, nnet, schedule, **kwargs):
 
 
 __all__ = ["Schedule", "stable_diffusion_beta_schedule", "LSimple", "LSimple_sde_sample", "HipTrainState",
-           "drop_labels", "customized_lr", "average_gradients", "int2bits"]
+           "drop_labels", "customized_lr", "average_gradients", "int2bits", "stateless_params"]
