@@ -463,8 +463,9 @@ int pdm_clip_encode(pdm_clip* c, const int64_t* ids, int batch, int L, float* ou
 
 /* ---- training step: LSimple (sde.py:270-279, train_ldm_discrete.py:87-90) + AdamW + EMA (train_ldm_discrete.py:
  * 159-175, utils.py:308-345) of the class-conditional / unconditional U-ViT (libs/uvit.py) and of the panoptic t2i
- * U-ViT (libs/uvit_t2i.py, separate streams: train_t2i_discrete.py:148-224, 466-473); head dim 64 (<= 608 tokens per
- * stream) or 72 (U-ViT-H, <= 415), mlp_time_embed = False ----------------------------------------------------------------------------------
+ * U-ViT (libs/uvit_t2i.py, separate streams: train_t2i_discrete.py:148-224, 466-473); head dim 64 or 72 (U-ViT-H),
+ * any number of tokens per stream with tokens * embed_dim < 2^31 (streams of <= 608 tokens at head dim 64, <= 415 at
+ * 72, keep the head-in-LDS attention backward; longer ones take the streaming one), mlp_time_embed = False -------------
  * All parameters live in one caller-owned flat fp32 buffer; pdm_train_param_info gives each reference state_dict
  * key its element offset and count (256-B aligned, ordered head / out-blocks last..first / mid / in-blocks
  * last..first / embeddings, so each block's gradients are one contiguous range).  The caller also owns a gradient
@@ -522,7 +523,13 @@ int pdm_grad_norm_clip(float* g, float* g2, long long n, float max_norm, float* 
 /* the backward kernels on their own (parity tests).  pdm_wgrad: C[n][k] (+)= sum_m A[m][n] B[m][k] (bf16 A [M][lda],
  * B [M][ldb], fp32 C [N][ldc]; scratch for split-reduction partials, may be NULL).  pdm_attention_backward: softmax
  * attention over packed qkv [B*L][3*H*Dh] with output o [B*L][H*Dh] and its gradient dout -> dqkv (Dh 64, L <= 608;
- * Dh 72, L <= 415).
+ * Dh 72, L <= 415: one workgroup per (sequence, head) with the head in LDS; it has no scratch, so it rejects longer
+ * sequences).  pdm_attention_backward_ex: the same with algo 0 (those kernels up to their limits, the streaming
+ * kernels above), 1 (those kernels only) or 2 (the streaming kernels at any L >= 1: one workgroup per (sequence, head,
+ * 128 rows), three launches, no atomics, the same bits on every run).  The streaming kernels need
+ * pdm_attention_backward_scratch_size bytes of 16-byte aligned scratch (>= 2 B H L floats; it need not be cleared);
+ * PDM_ERR_ARG before any launch for a scratch that is missing, misaligned or too small, an unknown algo, a head dim
+ * other than 64 / 72 or B * H * ceil(L / 128) >= 2^31.
  * pdm_layernorm_backward: nn.LayerNorm(D) over fp32 rows x, dh the output gradient (fp32, or bf16 if dh_bf16) ->
  * dx (+= if accumulate), optional bf16 copy dxb, dgamma, dbeta (written); scratch >= (4 ceil(rows/4) + 1) 8 D bytes
  * is plenty. */
@@ -532,6 +539,9 @@ int pdm_wgrad(const void* A, int lda, const void* B, int ldb, float* C, int ldc,
               float* scratch, size_t scratch_bytes, void* stream);
 int pdm_attention_backward(const void* qkv, const void* o, const void* dout, void* dqkv, int B, int L, int H, int Dh,
                            void* stream);
+int pdm_attention_backward_scratch_size(int B, int L, int H, int Dh, size_t* bytes);
+int pdm_attention_backward_ex(const void* qkv, const void* o, const void* dout, void* dqkv, int B, int L, int H, int Dh,
+                              int algo, void* scratch, size_t scratch_bytes, void* stream);
 int pdm_layernorm_backward(const float* x, const void* dh, int dh_bf16, const float* gamma, float* dx, void* dxb,
                            float* dgamma, float* dbeta, int rows, int D, int accumulate, float* scratch,
                            size_t scratch_bytes, void* stream);

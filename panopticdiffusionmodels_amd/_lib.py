@@ -267,6 +267,9 @@ _SIGS = {
                                  ctypes.c_size_t, ctypes.c_void_p]),
     "pdm_attention_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "pdm_attention_backward_scratch_size": (ctypes.c_int, [ctypes.c_int] * 4 + [ctypes.POINTER(ctypes.c_size_t)]),
+    "pdm_attention_backward_ex": (ctypes.c_int, [ctypes.c_void_p] * 4 + [ctypes.c_int] * 5 +
+                                  [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
     "pdm_layernorm_backward": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
@@ -861,14 +864,31 @@ def wgrad(dy, x, out=None, accumulate=False, scratch_mb=64):
     return out
 
 
-def attention_backward(qkv, o, dout, B, L, H, Dh=64):
+# what pdm_attention_backward (no scratch, the head-in-LDS kernels) takes per head dim (include/pdm.h)
+_ATTN_BWD_MAXL = {64: 608, 72: 415}
+
+
+def attention_backward(qkv, o, dout, B, L, H, Dh=64, algo=0, out=None, scratch=None):
     """d qkv (bf16 [B*L, 3*H*Dh]) of softmax attention (scale Dh^-0.5) from the forward's packed qkv, its output o
-    and the output gradient dout (pdm_attention_backward)."""
+    and the output gradient dout.  algo 0: the head-in-LDS kernels up to their limits (Dh 64: L <= 608, Dh 72:
+    L <= 415), the streaming kernels above; 1: the former only; 2: the streaming kernels at any L.  Goes through
+    pdm_attention_backward_ex with a scratch allocated here (or `scratch`, an fp32 tensor of at least
+    pdm_attention_backward_scratch_size bytes); a plain call within the old limits keeps the scratch-free
+    pdm_attention_backward, which runs the same kernels.  out: where to write (>= B*L rows of qkv's layout)."""
     lib = load()
     require_gpu(qkv)
-    dqkv = torch.empty_like(qkv)
-    check(lib.pdm_attention_backward(ptr(qkv), ptr(o), ptr(dout), ptr(dqkv), B, L, H, Dh, stream_ptr(qkv.device)),
-          "pdm_attention_backward")
+    dqkv = torch.empty_like(qkv) if out is None else out
+    if algo == 0 and scratch is None and L <= _ATTN_BWD_MAXL.get(Dh, 0):
+        check(lib.pdm_attention_backward(ptr(qkv), ptr(o), ptr(dout), ptr(dqkv), B, L, H, Dh, stream_ptr(qkv.device)),
+              "pdm_attention_backward")
+        return dqkv
+    if scratch is None:
+        nbytes = ctypes.c_size_t(0)
+        check(lib.pdm_attention_backward_scratch_size(B, L, H, Dh, ctypes.byref(nbytes)),
+              "pdm_attention_backward_scratch_size")
+        scratch = torch.empty((nbytes.value + 3) // 4, dtype=torch.float32, device=qkv.device)
+    check(lib.pdm_attention_backward_ex(ptr(qkv), ptr(o), ptr(dout), ptr(dqkv), B, L, H, Dh, int(algo), ptr(scratch),
+                                        scratch.numel() * 4, stream_ptr(qkv.device)), "pdm_attention_backward_ex")
     return dqkv
 
 

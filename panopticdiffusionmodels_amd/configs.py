@@ -7,6 +7,10 @@ Shapes and hyper-parameters are restated from the reference's config files:
   * imagenet512_uvit_huge   configs/imagenet512_uvit_huge.py:41-55,62-70
   * mscoco_uvit_small       configs/mscoco_uvit_small.py:41-55,63-70 (minus `patch_factor`,
     which libs/uvit_t2i.py:259-261 rejects)
+  * mscoco_uvit_small_512   configs/mscoco_uvit_small_512.py:13-72: the 512^2 text-to-image run on a 64 x 64 latent
+    (1 time + 77 context + 1024 patch tokens: image stream 1102, mask stream 2126).  The reference file names no
+    panoptic flags, which leaves `separate` at its default False, a branch the port does not carry (the trainer and
+    HipNet run the separate streams only); the entry takes the panoptic flags of mscoco_uvit_small instead.
 
 `tiny_*` entries are the reduced shapes used for committed golden fixtures.
 """
@@ -52,6 +56,17 @@ CONFIGS = {
                   num_panoptic_class=8),
         z_shape=(4, 32, 32), front_end="dpm_solver_pp", cfg_scale=1.0, decode=True,
         scale_factor=0.23010, sample_steps=50, mini_batch_size=32, panoptic=True,
+    ),
+    "mscoco_uvit_small_512": dict(
+        nnet=dict(name="uvit_t2i", img_size=64, in_chans=4, patch_size=2, embed_dim=512, depth=12,
+                  num_heads=8, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=768,
+                  num_clip_token=77, enable_panoptic=True, use_ground_truth=False, separate=True,
+                  num_panoptic_class=8),
+        z_shape=(4, 64, 64), front_end="dpm_solver_pp", cfg_scale=1.0, decode=True,
+        scale_factor=0.23010, sample_steps=50, mini_batch_size=10, panoptic=True,
+        train=dict(batch_size=8, objective="discrete", p_uncond=0.1, ema_rate=0.9999),
+        optimizer=dict(name="adamw", lr=0.0002, weight_decay=0.03, betas=(0.9, 0.9)),
+        lr_scheduler=dict(name="customized", warmup_steps=5000),
     ),
     # ---- tiny shapes for committed fixtures --------------------------------------------
     "tiny_uvit_cond": dict(  # Dh = 32, L = 2 + 64 tokens, class-conditional, conv final layer
@@ -118,6 +133,27 @@ CONFIGS = {
         train=dict(batch_size=2, objective="discrete", p_uncond=0.0, ema_rate=0.9),
         optimizer=dict(name="adamw", lr=0.0002, weight_decay=0.03, betas=(0.99, 0.99)),
         lr_scheduler=dict(name="customized", warmup_steps=-1),
+    ),
+    # past the head-in-LDS attention backward (608 tokens at head dim 64, 415 at 72): the streaming kernels
+    "tiny_t2i_train_512": dict(  # tiny_t2i_train on a 64 x 64 latent: the 512^2 token counts (Lx 1102, Lm 2126)
+        nnet=dict(name="uvit_t2i", img_size=64, in_chans=4, patch_size=2, embed_dim=64, depth=2,
+                  num_heads=1, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=64,
+                  num_clip_token=77, enable_panoptic=True, use_ground_truth=False, separate=True,
+                  num_panoptic_class=8),
+        z_shape=(4, 64, 64), front_end="dpm_solver_pp", cfg_scale=1.0, decode=False,
+        sample_steps=50, mini_batch_size=2, panoptic=True,
+        train=dict(batch_size=2, objective="discrete", p_uncond=0.0, ema_rate=0.9),
+        optimizer=dict(name="adamw", lr=0.0002, weight_decay=0.03, betas=(0.99, 0.99)),
+        lr_scheduler=dict(name="customized", warmup_steps=-1),
+    ),
+    "tiny_uvit_train_h_long": dict(  # tiny_uvit_train_h on a 64 x 64 latent: head dim 72 at L = 2 + 1024
+        nnet=dict(name="uvit", img_size=64, patch_size=2, in_chans=4, embed_dim=576, depth=2,
+                  num_heads=8, mlp_ratio=2, qkv_bias=False, mlp_time_embed=False, num_classes=11),
+        z_shape=(4, 64, 64), front_end="dpm_solver_pp", cfg_scale=0.4, decode=False,
+        sample_steps=50, mini_batch_size=2,
+        train=dict(batch_size=4, objective="discrete", p_uncond=0.15, ema_rate=0.9),
+        optimizer=dict(name="adamw", lr=0.0002, weight_decay=0.03, betas=(0.99, 0.99)),
+        lr_scheduler=dict(name="customized", warmup_steps=5),
     ),
 }
 

@@ -59,7 +59,14 @@ struct AttnBwdArgs {
   bf16* dqkv; int lddq;
   int B, L, H, Dh;
   float scale;
+  // algo 0: the head-in-LDS kernels where they apply (Dh 64: L <= 608, Dh 72: L <= 415), above that the streaming
+  // kernels; 1: the head-in-LDS kernels only; 2: the streaming kernels at any L.  The streaming kernels need
+  // attn_bwd_scratch_bytes of fp32 scratch (per query the log-sum-exp and delta; every word read is written first).
+  int algo;
+  float* scratch; size_t scratch_bytes;
 };
+bool attn_bwd_streams(int algo, int L, int Dh);          // whether attn_bwd_launch takes the streaming path
+size_t attn_bwd_scratch_bytes(int B, int L, int H);     // what the streaming path needs
 const char* attn_bwd_check(const AttnBwdArgs& p);
 hipError_t attn_bwd_launch(const AttnBwdArgs& p, hipStream_t stream);
 

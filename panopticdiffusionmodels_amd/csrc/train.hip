@@ -121,6 +121,8 @@ struct SW {
 struct TWork {
   SW I, Q;   // the image (class-conditional: the only) stream; the t2i mask stream
   float *XF, *XTMP, *PRE, *EPS, *DPRED, *DPRE, *DHN, *DX, *DX2, *PART;
+  float* ABS;         // the streaming attention backward's lse / delta (streams past the head-in-LDS kernels only)
+  size_t abs_bytes;
   bf16 *HN, *DTOK, *PV, *DXB, *DXB2, *DH, *DG, *DATT, *DQKV;
   // t2i: per layer the bf16 mask-block output (all Lm rows; in-blocks: the mask long skip), the mask stream's
   // running input / final output and gradients, the context tokens, the mask head
@@ -204,6 +206,11 @@ TWork tlayout(const pdm_trainer* t, int rows, char* base) {
     w.PVM = (bf16*)take(Mp * t->Kpm_pad * 2);
   }
   w.PART = (float*)take(PART_BYTES);
+  // nothing for the streams the head-in-LDS attention backward takes: their workspace keeps its size
+  for (int L : {t->L, t->t2i ? t->Lm : 0})
+    if (L > 0 && pdm::attn_bwd_streams(0, L, t->Dh))
+      w.abs_bytes = std::max(w.abs_bytes, pdm::attn_bwd_scratch_bytes(rows, L, t->H));
+  w.ABS = (float*)take(w.abs_bytes);
   w.bytes = off;
   return w;
 }
@@ -342,6 +349,7 @@ int block_bwd(const TC& c, const SW& S, int sid, int b, int rows, float*& DX, bf
     a.dqkv = w.DQKV; a.lddq = 3 * D;
     a.B = rows; a.L = S.L; a.H = t->H; a.Dh = t->Dh;
     a.scale = 1.0f / sqrtf((float)t->Dh);
+    a.algo = 0; a.scratch = w.ABS; a.scratch_bytes = w.abs_bytes;
     TR_CHECK(pdm::attn_bwd_check(a));
     TR_HIP(pdm::attn_bwd_launch(a, c.s));
   }
@@ -667,11 +675,12 @@ int pdm_train_create(const pdm_uvit_cfg* cfg, pdm_trainer** out) {
   t->Kpm = t->PK;
   t->Kpm_pad = (t->Kpm + 7) & ~7;
   t->depth = c.depth; t->nhalf = c.depth / 2; t->nb = 2 * t->nhalf + 1;   // in-blocks, mid_block, out-blocks
-  const int Lmax = t->t2i ? t->Lm : t->L;
-  if (Lmax > (t->Dh == 64 ? 608 : 415) || t->P > 64 || t->P % 4 || (t->t2i && (t->PK > 64 || t->PK % 4 || t->K <= 0 || t->nctx <= 0 ||
+  // row-group strides (tokens * embed_dim floats) are 32-bit in the gathers and column sums
+  const long long Lmax = t->t2i ? (long long)t->L + t->n_patch : t->L;
+  if (Lmax * c.embed_dim > 0x7fffffffLL || t->P > 64 || t->P % 4 || (t->t2i && (t->PK > 64 || t->PK % 4 || t->K <= 0 || t->nctx <= 0 ||
                                                           t->clip <= 0 || t->clip % 64))) {
     delete t;
-    return pdm::set_error(PDM_ERR_ARG, "pdm_train: tokens per stream <= 608 (head dim 72: 415), p*p*C (and p*p*K) "
+    return pdm::set_error(PDM_ERR_ARG, "pdm_train: tokens per stream * embed_dim < 2^31, p*p*C (and p*p*K) "
                                        "<= 64 and a multiple of 4, clip_dim a multiple of 64");
   }
   const int D = t->D;
@@ -889,6 +898,30 @@ int pdm_attention_backward(const void* qkv, const void* o, const void* dout, voi
   a.dqkv = static_cast<bf16*>(dqkv); a.lddq = 3 * H * Dh;
   a.B = B; a.L = L; a.H = H; a.Dh = Dh;
   a.scale = 1.0f / sqrtf((float)Dh);
+  a.algo = 1;   // no scratch: the head-in-LDS kernels only
+  TR_CHECK(pdm::attn_bwd_check(a));
+  TR_HIP(pdm::attn_bwd_launch(a, (hipStream_t)stream));
+  return PDM_OK;
+}
+
+int pdm_attention_backward_scratch_size(int B, int L, int H, int Dh, size_t* bytes) {
+  if (!bytes || B <= 0 || L <= 0 || H <= 0 || (Dh != 64 && Dh != 72))
+    return pdm::set_error(PDM_ERR_ARG, "pdm_attention_backward_scratch_size: B, L, H positive, head dim 64 or 72");
+  *bytes = pdm::attn_bwd_scratch_bytes(B, L, H);
+  return PDM_OK;
+}
+
+int pdm_attention_backward_ex(const void* qkv, const void* o, const void* dout, void* dqkv, int B, int L, int H, int Dh,
+                              int algo, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!qkv || !o || !dout || !dqkv) return pdm::set_error(PDM_ERR_ARG, "pdm_attention_backward_ex: null pointer");
+  pdm::AttnBwdArgs a{};
+  a.qkv = static_cast<const bf16*>(qkv); a.ldq = 3 * H * Dh;
+  a.o = static_cast<const bf16*>(o); a.ldo = H * Dh;
+  a.dout = static_cast<const bf16*>(dout); a.lddo = H * Dh;
+  a.dqkv = static_cast<bf16*>(dqkv); a.lddq = 3 * H * Dh;
+  a.B = B; a.L = L; a.H = H; a.Dh = Dh;
+  a.scale = 1.0f / sqrtf((float)Dh);
+  a.algo = algo; a.scratch = static_cast<float*>(scratch); a.scratch_bytes = scratch_bytes;
   TR_CHECK(pdm::attn_bwd_check(a));
   TR_HIP(pdm::attn_bwd_launch(a, (hipStream_t)stream));
   return PDM_OK;

@@ -8,6 +8,8 @@
 //                      in HBM.  The long reduction (M = tokens) is split over workgroups into fp32 partials.
 //   * attn_bwd_kernel  softmax attention backward for one (sequence, head) per workgroup, Q K V dO resident in LDS
 //                      (L <= 288) or two of them at a time (L <= 608: the t2i image / mask streams)
+//   * attn_bwd_pre / dkv / dq kernels  the same backward for any L: one workgroup per (sequence, head, 128 rows), the
+//                      other operand streamed through an LDS ring (the 512^2 t2i streams: 1102 / 2126 tokens)
 //   * LayerNorm / GELU / bias / embedding / final conv / decoder_pred backward, the LSimple loss, AdamW + EMA,
 //     the global gradient norm and its clipping (train.py:89-90).
 #include <algorithm>
@@ -614,6 +616,299 @@ __global__ __launch_bounds__(LONG ? AB_THREADS_LONG : AB_THREADS, 1) void attn_b
 }
 
 // ------------------------------------------------------------------------------------------------
+// Streaming attention backward: any L, head dims 64 / 72, parallel over the sequence as well as over (sequence, head).
+// Three launches, each with one workgroup (8 waves) per (sequence, head, block of 128 rows), no sums across
+// workgroups and no atomics, so the same inputs give the same bits:
+//   pre   per query (wave: 16 queries, Q rows in registers), keys streamed: lse2[q] (online max / sum over 64-key
+//         tiles) and delta[q] -> fp32 scratch [2][B*H][Lr], Lr = L rounded up to 128; rows L .. Lr get 0 / 0
+//   dkv   per key (wave: 16 keys, K / V rows in registers), Q / dO streamed: pass A of attn_bwd_kernel
+//   dq    per query (wave: 16 queries, Q / dO rows in registers), K / V streamed: pass B of attn_bwd_kernel
+// S is recomputed in dkv and in dq (seven MFMA products instead of five).  The streamed operand goes through a
+// double-buffered LDS ring of 64-row tiles in the images of attn_bwd_kernel (ab_off), filled by plain loads into
+// registers before a tile's MFMAs and LDS stores after them (one barrier per tile).  Rows >= L of a tile are zero: a
+// padded query has Q = dO = 0, lse2 = delta = 0, so P = 1, dS = 0 and it adds exactly zero to dK and dV; a padded key
+// is masked (-inf in pre, P = 0 in dq).  Every global row is addressed inside its own sequence and rows >= L are
+// neither read nor written.
+constexpr int AS_THREADS = 512, AS_BLK = 128, AS_TILE = 64;
+
+template <int DH>
+struct AsDims {
+  static constexpr int NCHR = DH == 64 ? 8 : 12, NCH = DH / 8, KK = NCHR / 4, NDT = (DH + 15) / 16, ROWB = NCHR * 16;
+};
+
+// 16-B chunk c of row r of image img (0 Q, 1 K, 2 V, 3 dO) of head h of the sequence starting at row0; zeros for the
+// rows >= L and for the padding chunks of Dh 72
+template <int DH>
+__device__ __forceinline__ bf16x8 as_grow(const AttnBwdArgs& p, size_t row0, int h, int img, int r, int c) {
+  if (c >= DH / 8 || r >= p.L) return bf16x8{};
+  const bf16* src = img < 3 ? p.qkv + (row0 + r) * p.ldq + img * (p.H * DH) + h * DH + c * 8
+                            : p.dout + (row0 + r) * p.lddo + h * DH + c * 8;
+  return *reinterpret_cast<const bf16x8*>(src);
+}
+
+// one 64-row tile of NIMG images on its way from global memory (load) to an LDS ring slot (store)
+template <int DH, int NIMG>
+struct AsTile {
+  static constexpr int NCHR = AsDims<DH>::NCHR, ROWB = AsDims<DH>::ROWB;
+  static constexpr int TOT = NIMG * AS_TILE * NCHR, CNT = (TOT + AS_THREADS - 1) / AS_THREADS;
+  bf16x8 v[CNT];
+  __device__ __forceinline__ void load(const AttnBwdArgs& p, size_t row0, int h, int im0, int im1, int r0, int tid) {
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      const int e = tid + i * AS_THREADS;
+      const int im = e / (AS_TILE * NCHR), r = (e / NCHR) % AS_TILE, c = e % NCHR;
+      v[i] = e < TOT ? as_grow<DH>(p, row0, h, im ? im1 : im0, r0 + r, c) : bf16x8{};
+    }
+  }
+  __device__ __forceinline__ void store(char* slot, int tid) const {
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) {
+      const int e = tid + i * AS_THREADS;
+      const int im = e / (AS_TILE * NCHR), r = (e / NCHR) % AS_TILE, c = e % NCHR;
+      if (e < TOT) *reinterpret_cast<bf16x8*>(slot + im * AS_TILE * ROWB + ab_off<NCHR>(r, c)) = v[i];
+    }
+  }
+};
+
+template <int DH>
+__global__ __launch_bounds__(AS_THREADS) void attn_bwd_pre_kernel(AttnBwdArgs p, int nblk, int Lr) {
+  using Dm = AsDims<DH>;
+  constexpr int NCHR = Dm::NCHR, NCH = Dm::NCH, KK = Dm::KK, ROWB = Dm::ROWB;
+  __shared__ __attribute__((aligned(16))) char ring[2][AS_TILE * ROWB];
+  const int L = p.L;
+  const int bh = blockIdx.x / nblk, blk = blockIdx.x - bh * nblk, b = bh / p.H, h = bh - b * p.H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, col = lane & 15;
+  const size_t row0 = (size_t)b * L;
+  const float cs = p.scale * 1.4426950408889634f;
+  float* lse_g = p.scratch + (size_t)bh * Lr;
+  float* dlt_g = p.scratch + ((size_t)p.B * p.H + bh) * Lr;
+  if (tid < AS_BLK) {   // delta[q] = sum_d dO[q][d] O[q][d]
+    const int q = blk * AS_BLK + tid;
+    float d = 0.f;
+    if (q < L) {
+      const bf16* orow = p.o + (row0 + q) * p.ldo + h * DH;
+      const bf16* drow = p.dout + (row0 + q) * p.lddo + h * DH;
+#pragma unroll
+      for (int c = 0; c < NCH; ++c) {
+        const bf16x8 ov = *reinterpret_cast<const bf16x8*>(orow + c * 8);
+        const bf16x8 dv = *reinterpret_cast<const bf16x8*>(drow + c * 8);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) d += (float)ov[j] * (float)dv[j];
+      }
+    }
+    dlt_g[q] = d;
+  }
+  const int q = blk * AS_BLK + wave * 16 + col;
+  bf16x8 qr[KK];
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk) qr[kk] = as_grow<DH>(p, row0, h, 0, q, kk * 4 + g);
+  const int nt = (L + AS_TILE - 1) / AS_TILE;
+  AsTile<DH, 1> st;
+  st.load(p, row0, h, 1, 1, 0, tid);
+  st.store(ring[0], tid);
+  __syncthreads();
+  float m = -INFINITY, l = 0.f;
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) st.load(p, row0, h, 1, 1, (t + 1) * AS_TILE, tid);
+    const char* Ks = ring[t & 1];
+    {   // the tile's 64 keys in one online-softmax step: four independent S tiles, one max / sum exchange
+      f32x4 s[AS_TILE / 16];
+#pragma unroll
+      for (int i = 0; i < AS_TILE / 16; ++i) {
+        s[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk)   // S^T[key][q]: A = K rows, B = Q rows
+          s[i] = mfma16x16x32(ab_row<NCHR>(Ks, i * 16 + col, kk * 4 + g), qr[kk], s[i]);
+      }
+      // lane: query q, keys t*64 + 16i + 4g + j
+      float tmax = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < AS_TILE / 16; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          s[i][j] = (t * AS_TILE + i * 16 + 4 * g + j < L) ? s[i][j] * cs : -INFINITY;
+          tmax = fmaxf(tmax, s[i][j]);
+        }
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+      tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+      const float mn = fmaxf(m, tmax);   // finite: the tile's first key is < L
+      float ts = 0.f;
+#pragma unroll
+      for (int i = 0; i < AS_TILE / 16; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ts += exp2f(s[i][j] - mn);
+      ts += __shfl_xor(ts, 16, 64);
+      ts += __shfl_xor(ts, 32, 64);
+      l = l * exp2f(m - mn) + ts;
+      m = mn;
+    }
+    if (t + 1 < nt) st.store(ring[(t + 1) & 1], tid);
+    __syncthreads();
+  }
+  if (g == 0) lse_g[q] = q < L ? m + log2f(l) : 0.f;
+}
+
+template <int DH>
+__global__ __launch_bounds__(AS_THREADS) void attn_bwd_dkv_kernel(AttnBwdArgs p, int nblk, int Lr) {
+  using Dm = AsDims<DH>;
+  constexpr int NCHR = Dm::NCHR, KK = Dm::KK, NDT = Dm::NDT, ROWB = Dm::ROWB;
+  __shared__ __attribute__((aligned(16))) char ring[2][2 * AS_TILE * ROWB];   // per slot [Q | dO]
+  __shared__ float ls[2][2][AS_TILE];                                        // per slot lse2, delta
+  const int L = p.L;
+  const int bh = blockIdx.x / nblk, blk = blockIdx.x - bh * nblk, b = bh / p.H, h = bh - b * p.H;
+  const int D = p.H * DH;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, col = lane & 15;
+  const size_t row0 = (size_t)b * L;
+  const float cs = p.scale * 1.4426950408889634f;
+  // tid < 64: lse2, 64 <= tid < 128: delta of the tile's row tid & 63
+  const float* ls_g = p.scratch + ((size_t)(tid >> 6 & 1) * p.B * p.H + bh) * Lr + (tid & 63);
+  const int key = blk * AS_BLK + wave * 16 + col;
+  bf16x8 kr[KK], vr[KK];
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk) {
+    kr[kk] = as_grow<DH>(p, row0, h, 1, key, kk * 4 + g);
+    vr[kk] = as_grow<DH>(p, row0, h, 2, key, kk * 4 + g);
+  }
+  f32x4 dv[NDT], dk[NDT];
+#pragma unroll
+  for (int i = 0; i < NDT; ++i) { dv[i] = f32x4{0.f, 0.f, 0.f, 0.f}; dk[i] = dv[i]; }
+  const int nt = (L + AS_TILE - 1) / AS_TILE;   // nt * 64 <= Lr
+  AsTile<DH, 2> st;
+  float lv = 0.f;
+  st.load(p, row0, h, 0, 3, 0, tid);
+  if (tid < 2 * AS_TILE) lv = ls_g[0];
+  st.store(ring[0], tid);
+  if (tid < 2 * AS_TILE) ls[0][tid >> 6][tid & 63] = lv;
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) {
+      st.load(p, row0, h, 0, 3, (t + 1) * AS_TILE, tid);
+      if (tid < 2 * AS_TILE) lv = ls_g[(t + 1) * AS_TILE];
+    }
+    const char* Qs = ring[t & 1];
+    const char* Os = Qs + AS_TILE * ROWB;
+    const float* lse = ls[t & 1][0];
+    const float* dlt = ls[t & 1][1];
+    for (int q0 = 0; q0 < AS_TILE && t * AS_TILE + q0 < L; q0 += 32) {
+      f32x4 s[2], dp[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {   // S[q][key] / dP[q][key]: A = Q / dO rows (q), B = K / V rows (key)
+        s[hh] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dp[hh] = s[hh];
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+          s[hh] = mfma16x16x32(ab_row<NCHR>(Qs, q0 + hh * 16 + col, kk * 4 + g), kr[kk], s[hh]);
+          dp[hh] = mfma16x16x32(ab_row<NCHR>(Os, q0 + hh * 16 + col, kk * 4 + g), vr[kk], dp[hh]);
+        }
+      }
+      // lane: its key, queries q0 + hh*16 + 4g + j
+      bf16x8 pf, sf;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int q = q0 + hh * 16 + 4 * g + j;
+          const float pv = exp2f(s[hh][j] * cs - lse[q]);
+          pf[hh * 4 + j] = (bf16)pv;
+          sf[hh * 4 + j] = (bf16)(pv * (dp[hh][j] - dlt[q]));
+        }
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) {
+        dv[dt] = mfma16x16x32(ab_trT<NCHR>(Os, q0, dt * 16, lane), pf, dv[dt]);
+        dk[dt] = mfma16x16x32(ab_trT<NCHR>(Qs, q0, dt * 16, lane), sf, dk[dt]);
+      }
+    }
+    if (t + 1 < nt) {
+      st.store(ring[(t + 1) & 1], tid);
+      if (tid < 2 * AS_TILE) ls[(t + 1) & 1][tid >> 6][tid & 63] = lv;
+    }
+    __syncthreads();
+  }
+  // lane: its key, d = dt*16 + 4g + {0..3}
+  if (key < L) {
+    bf16* drow = p.dqkv + (row0 + key) * p.lddq + h * DH;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      const int d = dt * 16 + 4 * g;
+      if (d >= DH) break;
+      *reinterpret_cast<bf16x4*>(drow + D + d) =
+          to_bf16x4(dk[dt][0] * p.scale, dk[dt][1] * p.scale, dk[dt][2] * p.scale, dk[dt][3] * p.scale);
+      *reinterpret_cast<bf16x4*>(drow + 2 * D + d) = to_bf16x4(dv[dt][0], dv[dt][1], dv[dt][2], dv[dt][3]);
+    }
+  }
+}
+
+template <int DH>
+__global__ __launch_bounds__(AS_THREADS) void attn_bwd_dq_kernel(AttnBwdArgs p, int nblk, int Lr) {
+  using Dm = AsDims<DH>;
+  constexpr int NCHR = Dm::NCHR, KK = Dm::KK, NDT = Dm::NDT, ROWB = Dm::ROWB;
+  __shared__ __attribute__((aligned(16))) char ring[2][2 * AS_TILE * ROWB];   // per slot [K | V]
+  const int L = p.L;
+  const int bh = blockIdx.x / nblk, blk = blockIdx.x - bh * nblk, b = bh / p.H, h = bh - b * p.H;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, col = lane & 15;
+  const size_t row0 = (size_t)b * L;
+  const float cs = p.scale * 1.4426950408889634f;
+  const int q = blk * AS_BLK + wave * 16 + col;   // < Lr
+  const float lq = p.scratch[(size_t)bh * Lr + q], dq_ = p.scratch[((size_t)p.B * p.H + bh) * Lr + q];
+  bf16x8 qr[KK], orr[KK];
+#pragma unroll
+  for (int kk = 0; kk < KK; ++kk) {
+    qr[kk] = as_grow<DH>(p, row0, h, 0, q, kk * 4 + g);
+    orr[kk] = as_grow<DH>(p, row0, h, 3, q, kk * 4 + g);
+  }
+  f32x4 dq[NDT];
+#pragma unroll
+  for (int i = 0; i < NDT; ++i) dq[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int nt = (L + AS_TILE - 1) / AS_TILE;
+  AsTile<DH, 2> st;
+  st.load(p, row0, h, 1, 2, 0, tid);
+  st.store(ring[0], tid);
+  __syncthreads();
+  for (int t = 0; t < nt; ++t) {
+    if (t + 1 < nt) st.load(p, row0, h, 1, 2, (t + 1) * AS_TILE, tid);
+    const char* Ks = ring[t & 1];
+    const char* Vs = Ks + AS_TILE * ROWB;
+    for (int k0 = 0; k0 < AS_TILE && t * AS_TILE + k0 < L; k0 += 32) {
+      f32x4 s[2], dp[2];
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh) {   // S^T[key][q]: A = K / V rows (key), B = Q / dO rows (q)
+        s[hh] = f32x4{0.f, 0.f, 0.f, 0.f};
+        dp[hh] = s[hh];
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+          s[hh] = mfma16x16x32(ab_row<NCHR>(Ks, k0 + hh * 16 + col, kk * 4 + g), qr[kk], s[hh]);
+          dp[hh] = mfma16x16x32(ab_row<NCHR>(Vs, k0 + hh * 16 + col, kk * 4 + g), orr[kk], dp[hh]);
+        }
+      }
+      // lane: its query, keys t*64 + k0 + hh*16 + 4g + j
+      bf16x8 sf;
+#pragma unroll
+      for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int key = t * AS_TILE + k0 + hh * 16 + 4 * g + j;
+          const float pv = key < L ? exp2f(s[hh][j] * cs - lq) : 0.f;
+          sf[hh * 4 + j] = (bf16)(pv * (dp[hh][j] - dq_));
+        }
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) dq[dt] = mfma16x16x32(ab_trT<NCHR>(Ks, k0, dt * 16, lane), sf, dq[dt]);
+    }
+    if (t + 1 < nt) st.store(ring[(t + 1) & 1], tid);
+    __syncthreads();
+  }
+  if (q < L) {
+    bf16* drow = p.dqkv + (row0 + q) * p.lddq + h * DH;
+#pragma unroll
+    for (int dt = 0; dt < NDT; ++dt) {
+      const int d = dt * 16 + 4 * g;
+      if (d >= DH) break;
+      *reinterpret_cast<bf16x4*>(drow + d) =
+          to_bf16x4(dq[dt][0] * p.scale, dq[dt][1] * p.scale, dq[dt][2] * p.scale, dq[dt][3] * p.scale);
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 // LSimple (sde.py:270-279 / train_ldm_discrete.py:87-90): loss[b] = mean_j (target - pred)^2 (mos), and the
 // gradient of gscale * sum_b loss[b] w.r.t. pred: -2 gscale (target - pred) / per
 // tanh_bwd: pred = tanh(u) (the t2i mask head, libs/uvit_t2i.py:513) and dpred is the gradient w.r.t. u
@@ -1044,16 +1339,49 @@ hipError_t gelu_bwd_launch(bf16* dg, const bf16* u, long long n, hipStream_t str
   return hipGetLastError();
 }
 
+bool attn_bwd_streams(int algo, int L, int Dh) {
+  return algo == 2 || (algo == 0 && L > (Dh == 64 ? AB_MAXL_LONG : AB_MAXL_72));
+}
+
+size_t attn_bwd_scratch_bytes(int B, int L, int H) {
+  const size_t Lr = ((size_t)L + AS_BLK - 1) / AS_BLK * AS_BLK;
+  return 2 * (size_t)B * H * Lr * sizeof(float);
+}
+
 const char* attn_bwd_check(const AttnBwdArgs& p) {
   if (p.Dh != 64 && p.Dh != 72) return "attention backward: head dim 64 or 72";
-  if (p.L <= 0 || p.L > (p.Dh == 64 ? AB_MAXL_LONG : AB_MAXL_72))
-    return "attention backward: 1 <= L <= 608 (head dim 64) / 415 (72): two of the head's Q, K, V, dO in LDS at a time";
+  if (p.algo < 0 || p.algo > 2) return "attention backward: algo 0 (automatic), 1 (head in LDS) or 2 (streaming)";
   if (p.B <= 0 || p.H <= 0) return "attention backward: B, H must be positive";
   if (p.ldq % 8 || p.ldo % 8 || p.lddo % 8 || p.lddq % 4) return "attention backward: row strides must be 16-byte multiples";
+  if (p.L <= 0) return "attention backward: L must be positive";
+  if (!attn_bwd_streams(p.algo, p.L, p.Dh)) {
+    if (p.L > (p.Dh == 64 ? AB_MAXL_LONG : AB_MAXL_72))
+      return "attention backward: 1 <= L <= 608 (head dim 64) / 415 (72): two of the head's Q, K, V, dO in LDS at a time; "
+             "the streaming kernels of pdm_attention_backward_ex take any L";
+    return nullptr;
+  }
+  // one workgroup per (sequence, head, 128-row block) on grid.x; L + 127 in 32 bits
+  if (p.L > (1 << 30) || (long long)p.B * p.H * ((p.L + AS_BLK - 1) / AS_BLK) > 0x7fffffffLL)
+    return "attention backward (streaming): B * H * ceil(L / 128) must be below 2^31";
+  if (!p.scratch || ((uintptr_t)p.scratch & 15)) return "attention backward (streaming): scratch must be 16-byte aligned";
+  if (p.scratch_bytes < attn_bwd_scratch_bytes(p.B, p.L, p.H))
+    return "attention backward (streaming): scratch too small (pdm_attention_backward_scratch_size)";
   return nullptr;
 }
 
+template <int DH>
+static hipError_t attn_bwd_stream_launch(const AttnBwdArgs& p, hipStream_t stream) {
+  const int nblk = (p.L + AS_BLK - 1) / AS_BLK, Lr = nblk * AS_BLK;
+  const dim3 grid(p.B * p.H * nblk), block(AS_THREADS);
+  hipLaunchKernelGGL((attn_bwd_pre_kernel<DH>), grid, block, 0, stream, p, nblk, Lr);
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<DH>), grid, block, 0, stream, p, nblk, Lr);
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<DH>), grid, block, 0, stream, p, nblk, Lr);
+  return hipGetLastError();
+}
+
 hipError_t attn_bwd_launch(const AttnBwdArgs& p, hipStream_t stream) {
+  if (attn_bwd_streams(p.algo, p.L, p.Dh))
+    return p.Dh == 72 ? attn_bwd_stream_launch<72>(p, stream) : attn_bwd_stream_launch<64>(p, stream);
   const int Lp = (p.L + 31) & ~31;
   static bool attr = false;
   if (!attr) {
