@@ -73,6 +73,22 @@ int pdm_gemm_sk_stats(unsigned long long* out3);
  * (a measurement hook with no reference counterpart) */
 int pdm_gemm_seg_stats(unsigned long long* out25);
 int pdm_set_attention_algo(int algo);
+/* What pdm_attention / pdm_attention_log2 would launch for a shape, with no side effect (no device call, and the global
+ * set by pdm_set_attention_algo is neither read nor changed: `algo` is that knob's value as an argument, which also
+ * takes 10 = head-resident v2 with the row sums on the VALU).  The attention launcher takes its decisions from this
+ * same function.  ncu: compute units of the device (0: the launcher's default, 256).  out6 = {family (below), waves
+ * per workgroup, tail1 (the last key block holds 1..16 keys behind a full one and the kernel resolves it at compile
+ * time), timing variant (0 the real kernel, 1 loads only, 2 math only), grid size in workgroups, dynamic LDS bytes}.
+ * PDM_ERR_ARG for a shape pdm_attention rejects, an algo outside 0..16, ncu < 0 or a null out6. */
+#define PDM_ATTN_STREAMED 0   /* K/V streamed through LDS per 64-query block (any head dim, any L) */
+#define PDM_ATTN_KV2 1        /* head-resident, 2 query tiles per wave (algo 2) */
+#define PDM_ATTN_KV3 2        /* head-resident, 3 query tiles per wave (algo 3) */
+#define PDM_ATTN_V2 3         /* head-resident v2, Dh 64, one workgroup per head */
+#define PDM_ATTN_V2_VALU 4    /* the same with VALU row sums (algo 10) */
+#define PDM_ATTN_V3 5         /* persistent head-resident, Dh 64 */
+#define PDM_ATTN_H72 6        /* head-resident Dh 72, one workgroup per head */
+#define PDM_ATTN_H72P 7       /* persistent head-resident Dh 72 */
+int pdm_attention_plan(int B, int L, int H, int Dh, int algo, int ncu, int* out6);
 
 /* ---- network handle: libs/uvit.py:138-230 UViT, libs/uvit_t2i.py:258-525 UViT (t2i) -------------- */
 typedef struct pdm_uvit pdm_uvit;

@@ -4,6 +4,7 @@ The product path has no fallback: if the HIP library is missing, cannot be loade
 present, calls raise.  Status codes map to the exception types of the reference (ValueError for bad
 arguments / unsupported shapes, RuntimeError otherwise).
 """
+import collections
 import ctypes
 import os
 
@@ -112,6 +113,7 @@ _SIGS = {
     "pdm_gemm_sk_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     "pdm_gemm_seg_stats": (ctypes.c_int, [ctypes.POINTER(ctypes.c_ulonglong)]),
     "pdm_set_attention_algo": (ctypes.c_int, [ctypes.c_int]),
+    "pdm_attention_plan": (ctypes.c_int, [ctypes.c_int] * 6 + [ctypes.POINTER(ctypes.c_int)]),
     "pdm_set_gemm_tuning": (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),
     "pdm_uvit_create": (ctypes.c_int, [ctypes.POINTER(PdmUvitCfg), ctypes.POINTER(ctypes.c_void_p)]),
     "pdm_uvit_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -724,11 +726,32 @@ def layernorm(x, gamma, beta, eps=1e-5):
     return y
 
 
-def attention(qkv, B, L, H, Dh, scale=None, q_log2=False):
-    """q_log2: q already carries Dh^-0.5 * log2(e) (pdm_attention_log2, the U-ViT forward's layout)."""
+ATTENTION_FAMILIES = ("streamed", "kv2", "kv3", "v2", "v2_valu", "v3", "h72", "h72p")   # PDM_ATTN_* of include/pdm.h
+AttentionPlan = collections.namedtuple("AttentionPlan", "family waves tail1 variant grid lds_bytes")
+
+
+def attention_plan(B, L, H, Dh, algo=0, ncu=256):
+    """What `attention` launches for this shape under pdm_set_attention_algo(algo) on a device of ncu compute units:
+    AttentionPlan(family name, waves per workgroup, tail1, timing variant 0/1/2, grid, dynamic LDS bytes).  Pure
+    host code (no GPU, no global read or changed); the launcher decides with the same function."""
+    out = (ctypes.c_int * 6)()
+    check(load().pdm_attention_plan(B, L, H, Dh, int(algo), int(ncu), out), "pdm_attention_plan")
+    return AttentionPlan(ATTENTION_FAMILIES[out[0]], out[1], bool(out[2]), out[3], out[4], out[5])
+
+
+def attention(qkv, B, L, H, Dh, scale=None, q_log2=False, out=None):
+    """q_log2: q already carries Dh^-0.5 * log2(e) (pdm_attention_log2, the U-ViT forward's layout).
+    qkv: bf16 rows of 3*H*Dh columns; its row stride is passed on (a multiple of 8 elements, so a view works).
+    out: where to write, bf16 with >= B*L rows of H*Dh columns and unit column stride (a view with its own row stride,
+    a multiple of 4 elements, is fine); allocated here when None."""
     lib = load()
     require_gpu(qkv)
-    out = torch.empty(B * L, H * Dh, dtype=torch.bfloat16, device=qkv.device)
+    if out is None:
+        out = torch.empty(B * L, H * Dh, dtype=torch.bfloat16, device=qkv.device)
+    elif (out.dtype != torch.bfloat16 or out.dim() != 2 or out.shape[0] < B * L or out.shape[1] != H * Dh
+          or out.stride(1) != 1 or out.device != qkv.device):
+        raise ValueError(f"attention: out must be bf16 [>= {B * L}, {H * Dh}] with unit column stride on {qkv.device}, "
+                         f"got {out.dtype} {tuple(out.shape)} strides {tuple(out.stride())} on {out.device}")
     if q_log2:
         check(lib.pdm_attention_log2(ptr(qkv), qkv.stride(0), ptr(out), out.stride(0), B, L, H, Dh,
                                      stream_ptr(qkv.device)), "pdm_attention_log2")

@@ -13,6 +13,7 @@
 // the row-major V chunk.
 #include <type_traits>
 
+#include "../../include/pdm.h"
 #include "pdm_common.h"
 #include "pdm_kernels.h"
 
@@ -1623,62 +1624,98 @@ static bool tail1(int L) { return L > 64 && L % 64 != 0 && L % 64 <= 16; }
 static int g_attention_algo = 0;   // 0 auto, 1 streamed K/V, 2/3 head-resident T = 2/3, 4 head-resident v2 (5/6 timing)
 void attention_set_algo(int algo) { g_attention_algo = algo; }
 
-hipError_t attention_launch(const AttentionArgs& args, hipStream_t stream) {
-  AttentionArgs p = args;
-  const int nqt = (p.L + 15) / 16;
-  int algo = g_attention_algo;
-  const int Lp = (p.L + 31) / 32 * 32;   // PV reads whole 32-key steps
+AttentionPlan attention_plan(int B, int L, int H, int Dh, int algo, int ncu) {
+  const int nqt = (L + 15) / 16, nbh = B * H;
+  const int Lp = (L + 31) / 32 * 32;   // PV reads whole 32-key steps
   // Dh = 72 (U-ViT-H): head-resident 64 + 8 kernel when two heads' K + V fit per CU (L <= 280); 7/8/9 = timing
   // variants (normal / loads only / math only); measured tools/attn_bench.py
-  const int LV = (p.L + 7) / 8 * 8, L16 = (p.L + 15) / 16 * 16;
+  const int LV = (L + 7) / 8 * 8, L16 = (L + 15) / 16 * 16;
   const int smem72 = (LV + L16) * 144;   // V rows read past LV (up to round32(L)) alias staged K rows below LV
+  const bool fits72 = Dh == 72 && smem72 <= 80 * 1024 && Lp <= 2 * LV;
+  const int smem64 = Lp * 256;           // Dh = 64: the head's K and V, 128 B per row each
+  const bool fits64 = Dh == 64 && smem64 <= 160 * 1024;
   // persistent Dh = 72 (14; 15 / 16 = loads-only / math-only timing): every wave owns a tile (nqt >= 4)
-  if (p.Dh == 72 && smem72 <= 80 * 1024 && (p.L + 31) / 32 * 32 <= 2 * LV && algo >= 14 && algo <= 16 && nqt >= 4) {
-    static bool attr72p = false;
-    static int ncu = 256;
-    if (!attr72p) {
-      (void)hipFuncSetAttribute((const void*)attention_h72p_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_h72p_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_h72p_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-        ncu = n;
-      attr72p = true;
-    }
-    const int nbh = p.B * p.H, slots = 2 * ncu;
-    const dim3 grid(nbh < slots ? nbh : slots), block(256);
-    if (algo == 15) hipLaunchKernelGGL(attention_h72p_kernel<1>, grid, block, smem72, stream, p, nqt, LV, L16);
-    else if (algo == 16) hipLaunchKernelGGL(attention_h72p_kernel<2>, grid, block, smem72, stream, p, nqt, LV, L16);
-    else hipLaunchKernelGGL(attention_h72p_kernel<0>, grid, block, smem72, stream, p, nqt, LV, L16);
-    return hipGetLastError();
-  }
-  if (algo >= 14 && algo <= 16) algo = p.Dh == 72 ? 7 : 0;
-  if (p.Dh == 72 && smem72 <= 80 * 1024 && (p.L + 31) / 32 * 32 <= 2 * LV && (algo == 0 || (algo >= 7 && algo <= 9))) {
-    static bool attr72 = false;
-    if (!attr72) {
-      (void)hipFuncSetAttribute((const void*)attention_h72_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_h72_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_h72_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_h72_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-      attr72 = true;
-    }
-    const dim3 grid(p.B * p.H), block(256);
-    if (algo == 8) hipLaunchKernelGGL(attention_h72_kernel<1>, grid, block, smem72, stream, p, nqt, LV, L16);
-    else if (algo == 9) hipLaunchKernelGGL(attention_h72_kernel<2>, grid, block, smem72, stream, p, nqt, LV, L16);
-    else if (tail1(p.L)) hipLaunchKernelGGL((attention_h72_kernel<0, 1>), grid, block, smem72, stream, p, nqt, LV, L16);
-    else hipLaunchKernelGGL(attention_h72_kernel<0>, grid, block, smem72, stream, p, nqt, LV, L16);
-    return hipGetLastError();
-  }
+  if (fits72 && algo >= 14 && algo <= 16 && nqt >= 4)
+    return {PDM_ATTN_H72P, 4, 0, algo - 14, nbh < 2 * ncu ? nbh : 2 * ncu, smem72};
+  if (algo >= 14 && algo <= 16) algo = Dh == 72 ? 7 : 0;
+  if (fits72 && (algo == 0 || (algo >= 7 && algo <= 9)))
+    return {PDM_ATTN_H72, 4, algo != 8 && algo != 9 && tail1(L), algo == 8 ? 1 : algo == 9 ? 2 : 0, nbh, smem72};
   // persistent v3 (11; 12 / 13 = loads-only / math-only timing): Dh = 64, every wave owns a tile (nqt >= NW).  The
   // automatic choice wherever it applies: L/2 at 100 rows 76.4 -> 66.6 us, 190 rows 143.5 -> 136.5, 50 rows 44.8 ->
   // 44.0, t2i 334 / 590 unchanged (tools/attn_bench.py, profiles/r05d/attn.log)
-  if (algo == 0 && p.Dh == 64 && Lp * 256 <= 160 * 1024) algo = 11;
-  if (algo >= 11 && algo <= 13 && p.Dh == 64 && Lp * 256 <= 160 * 1024) {
-    const int smem = Lp * 256;
-    const int nw = smem <= 80 * 1024 ? 4 : 8;
-    if (nqt >= nw) {
+  if (algo == 0 && fits64) algo = 11;
+  // two heads per CU: 4 waves each; one head per CU: 8 waves (two per SIMD)
+  const int nw64 = smem64 <= 80 * 1024 ? 4 : 8;
+  if (algo >= 11 && algo <= 13 && fits64) {
+    if (nqt >= nw64) {
+      const int slots = ncu * (nw64 == 4 ? 2 : 1);
+      return {PDM_ATTN_V3, nw64, algo == 11 && tail1(L), algo - 11, nbh < slots ? nbh : slots, smem64};
+    }
+    algo = 4;   // automatic below nqt = NW: the head-resident v2 structure (measured 152 vs 213 us streamed on L/2 at
+                // 190 rows, tools/attn_bench.py)
+  }
+  if (!fits64) algo = 1;
+  if (algo == 10) return {PDM_ATTN_V2_VALU, nw64, 0, 0, nbh, smem64};   // VALU row sums (A/B: 145.7 vs 140.1 us, L/2)
+  if (algo >= 4 && algo <= 6) return {PDM_ATTN_V2, nw64, 0, algo - 4, nbh, smem64};
+  if (algo == 2 || algo == 3) {
+    const int T = algo;
+    const int nw = (nqt + T - 1) / T;
+    if (nw <= (T == 2 ? 12 : 8)) return {T == 2 ? PDM_ATTN_KV2 : PDM_ATTN_KV3, nw, 0, 0, nbh, smem64};
+  }
+  const int nqb = (nqt + 3) / 4;
+  return {PDM_ATTN_STREAMED, 4, 0, 0, ((nbh + 7) / 8) * 8 * nqb, 0};
+}
+
+// compute units of the current device, asked once (the persistent kernels' grids); 256 if the runtime will not say
+static int attention_ncu() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+      return n;
+    return 256;
+  }();
+  return ncu;
+}
+
+hipError_t attention_launch(const AttentionArgs& args, hipStream_t stream) {
+  AttentionArgs p = args;
+  const int nqt = (p.L + 15) / 16;
+  const int Lp = (p.L + 31) / 32 * 32;
+  const int LV = (p.L + 7) / 8 * 8, L16 = (p.L + 15) / 16 * 16;
+  const AttentionPlan pl = attention_plan(p.B, p.L, p.H, p.Dh, g_attention_algo, attention_ncu());
+  const dim3 grid(pl.grid), block(pl.waves * 64);
+  const int smem = pl.lds_bytes;
+  switch (pl.family) {
+    case PDM_ATTN_H72P: {
+      static bool attr72p = false;
+      if (!attr72p) {
+        (void)hipFuncSetAttribute((const void*)attention_h72p_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_h72p_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_h72p_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        attr72p = true;
+      }
+      if (pl.variant == 1) hipLaunchKernelGGL(attention_h72p_kernel<1>, grid, block, smem, stream, p, nqt, LV, L16);
+      else if (pl.variant == 2) hipLaunchKernelGGL(attention_h72p_kernel<2>, grid, block, smem, stream, p, nqt, LV, L16);
+      else hipLaunchKernelGGL(attention_h72p_kernel<0>, grid, block, smem, stream, p, nqt, LV, L16);
+      return hipGetLastError();
+    }
+    case PDM_ATTN_H72: {
+      static bool attr72 = false;
+      if (!attr72) {
+        (void)hipFuncSetAttribute((const void*)attention_h72_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_h72_kernel<0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_h72_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_h72_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+        attr72 = true;
+      }
+      if (pl.variant == 1) hipLaunchKernelGGL(attention_h72_kernel<1>, grid, block, smem, stream, p, nqt, LV, L16);
+      else if (pl.variant == 2) hipLaunchKernelGGL(attention_h72_kernel<2>, grid, block, smem, stream, p, nqt, LV, L16);
+      else if (pl.tail1) hipLaunchKernelGGL((attention_h72_kernel<0, 1>), grid, block, smem, stream, p, nqt, LV, L16);
+      else hipLaunchKernelGGL(attention_h72_kernel<0>, grid, block, smem, stream, p, nqt, LV, L16);
+      return hipGetLastError();
+    }
+    case PDM_ATTN_V3: {
       static bool attr3 = false;
-      static int ncu = 256;
       if (!attr3) {
         (void)hipFuncSetAttribute((const void*)attention_v3_kernel<0, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attention_v3_kernel<0, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1688,91 +1725,70 @@ hipError_t attention_launch(const AttentionArgs& args, hipStream_t stream) {
         (void)hipFuncSetAttribute((const void*)attention_v3_kernel<0, 8, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attention_v3_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)attention_v3_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-          ncu = n;
         attr3 = true;
       }
-      const int nbh = p.B * p.H, slots = ncu * (nw == 4 ? 2 : 1);
-      const dim3 grid(nbh < slots ? nbh : slots);
-      if (nw == 4) {
-        if (algo == 11 && tail1(p.L)) hipLaunchKernelGGL((attention_v3_kernel<0, 4, 1>), grid, dim3(256), smem, stream, p, nqt, Lp);
-        else if (algo == 11) hipLaunchKernelGGL((attention_v3_kernel<0, 4>), grid, dim3(256), smem, stream, p, nqt, Lp);
-        else if (algo == 12) hipLaunchKernelGGL((attention_v3_kernel<1, 4>), grid, dim3(256), smem, stream, p, nqt, Lp);
-        else hipLaunchKernelGGL((attention_v3_kernel<2, 4>), grid, dim3(256), smem, stream, p, nqt, Lp);
+      if (pl.waves == 4) {
+        if (pl.tail1) hipLaunchKernelGGL((attention_v3_kernel<0, 4, 1>), grid, block, smem, stream, p, nqt, Lp);
+        else if (pl.variant == 0) hipLaunchKernelGGL((attention_v3_kernel<0, 4>), grid, block, smem, stream, p, nqt, Lp);
+        else if (pl.variant == 1) hipLaunchKernelGGL((attention_v3_kernel<1, 4>), grid, block, smem, stream, p, nqt, Lp);
+        else hipLaunchKernelGGL((attention_v3_kernel<2, 4>), grid, block, smem, stream, p, nqt, Lp);
       } else {
-        if (algo == 11 && tail1(p.L)) hipLaunchKernelGGL((attention_v3_kernel<0, 8, 1>), grid, dim3(512), smem, stream, p, nqt, Lp);
-        else if (algo == 11) hipLaunchKernelGGL((attention_v3_kernel<0, 8>), grid, dim3(512), smem, stream, p, nqt, Lp);
-        else if (algo == 12) hipLaunchKernelGGL((attention_v3_kernel<1, 8>), grid, dim3(512), smem, stream, p, nqt, Lp);
-        else hipLaunchKernelGGL((attention_v3_kernel<2, 8>), grid, dim3(512), smem, stream, p, nqt, Lp);
+        if (pl.tail1) hipLaunchKernelGGL((attention_v3_kernel<0, 8, 1>), grid, block, smem, stream, p, nqt, Lp);
+        else if (pl.variant == 0) hipLaunchKernelGGL((attention_v3_kernel<0, 8>), grid, block, smem, stream, p, nqt, Lp);
+        else if (pl.variant == 1) hipLaunchKernelGGL((attention_v3_kernel<1, 8>), grid, block, smem, stream, p, nqt, Lp);
+        else hipLaunchKernelGGL((attention_v3_kernel<2, 8>), grid, block, smem, stream, p, nqt, Lp);
       }
       return hipGetLastError();
     }
-    algo = 4;
-  }
-  if (p.Dh != 64 || Lp * 256 > 160 * 1024) algo = 1;
-  // automatic: the head-resident v2 structure wherever the head's K/V fit in LDS (Dh = 64: every U-ViT-S/M/L
-  // shape); measured 152 vs 213 us (streamed) on L/2 at 190 rows (tools/attn_bench.py)
-  if (algo == 0 && p.Dh == 64 && Lp * 256 <= 160 * 1024) algo = 4;
-  if (algo == 10 && p.Dh == 64 && Lp * 256 <= 160 * 1024) {   // v2 with VALU row sums (A/B: 145.7 vs 140.1 us, L/2)
-    const int smem = Lp * 256;
-    static bool attr10 = false;
-    if (!attr10) {
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr10 = true;
+    case PDM_ATTN_V2_VALU: {
+      static bool attr10 = false;
+      if (!attr10) {
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr10 = true;
+      }
+      if (pl.waves == 4) hipLaunchKernelGGL((attention_v2_kernel<0, 4, false>), grid, block, smem, stream, p, nqt, Lp);
+      else hipLaunchKernelGGL((attention_v2_kernel<0, 8, false>), grid, block, smem, stream, p, nqt, Lp);
+      return hipGetLastError();
     }
-    if (smem <= 80 * 1024) hipLaunchKernelGGL((attention_v2_kernel<0, 4, false>), dim3(p.B * p.H), dim3(256), smem, stream, p, nqt, Lp);
-    else hipLaunchKernelGGL((attention_v2_kernel<0, 8, false>), dim3(p.B * p.H), dim3(512), smem, stream, p, nqt, Lp);
-    return hipGetLastError();
-  }
-  if (algo >= 4 && algo <= 6 && p.Dh == 64 && Lp * 256 <= 160 * 1024) {
-    const int smem = Lp * 256;
-    static bool attr2 = false;
-    if (!attr2) {
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      (void)hipFuncSetAttribute((const void*)attention_v2_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr2 = true;
+    case PDM_ATTN_V2: {
+      static bool attr2 = false;
+      if (!attr2) {
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<0, 8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<1, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)attention_v2_kernel<2, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        attr2 = true;
+      }
+      if (pl.waves == 4) {
+        if (pl.variant == 0) hipLaunchKernelGGL((attention_v2_kernel<0, 4, true>), grid, block, smem, stream, p, nqt, Lp);
+        else if (pl.variant == 1) hipLaunchKernelGGL((attention_v2_kernel<1, 4>), grid, block, smem, stream, p, nqt, Lp);
+        else hipLaunchKernelGGL((attention_v2_kernel<2, 4>), grid, block, smem, stream, p, nqt, Lp);
+      } else {
+        if (pl.variant == 0) hipLaunchKernelGGL((attention_v2_kernel<0, 8, true>), grid, block, smem, stream, p, nqt, Lp);
+        else if (pl.variant == 1) hipLaunchKernelGGL((attention_v2_kernel<1, 8>), grid, block, smem, stream, p, nqt, Lp);
+        else hipLaunchKernelGGL((attention_v2_kernel<2, 8>), grid, block, smem, stream, p, nqt, Lp);
+      }
+      return hipGetLastError();
     }
-    const dim3 grid(p.B * p.H);
-    if (smem <= 80 * 1024) {   // two heads per CU: 4 waves each
-      if (algo == 4) hipLaunchKernelGGL((attention_v2_kernel<0, 4, true>), grid, dim3(256), smem, stream, p, nqt, Lp);
-      else if (algo == 5) hipLaunchKernelGGL((attention_v2_kernel<1, 4>), grid, dim3(256), smem, stream, p, nqt, Lp);
-      else hipLaunchKernelGGL((attention_v2_kernel<2, 4>), grid, dim3(256), smem, stream, p, nqt, Lp);
-    } else {                   // one head per CU: 8 waves (two per SIMD)
-      if (algo == 4) hipLaunchKernelGGL((attention_v2_kernel<0, 8, true>), grid, dim3(512), smem, stream, p, nqt, Lp);
-      else if (algo == 5) hipLaunchKernelGGL((attention_v2_kernel<1, 8>), grid, dim3(512), smem, stream, p, nqt, Lp);
-      else hipLaunchKernelGGL((attention_v2_kernel<2, 8>), grid, dim3(512), smem, stream, p, nqt, Lp);
-    }
-    return hipGetLastError();
+    default: break;
   }
   // the kernels below compute exp2(S * scale * log2 e): with q pre-scaled by scale * log2(e) (q_log2) they take
   // scale = ln 2 (the head-resident kernels above read q_log2 themselves and work in log2 units either way)
   if (p.q_log2) p.scale = 0.69314718055994531f;
-  if (algo == 0 || algo >= 4) algo = 1;
-  if (algo == 2 || algo == 3) {
-    const int T = algo;
-    const int nw = (nqt + T - 1) / T;
-    if (nw <= (T == 2 ? 12 : 8)) {
-      const int smem = Lp * 256;
-      static bool attr = false;
-      if (!attr) {
-        (void)hipFuncSetAttribute((const void*)attention_kv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)attention_kv_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        attr = true;
-      }
-      if (T == 2) hipLaunchKernelGGL(attention_kv_kernel<2>, dim3(p.B * p.H), dim3(nw * 64), smem, stream, p, nqt, Lp);
-      else hipLaunchKernelGGL(attention_kv_kernel<3>, dim3(p.B * p.H), dim3(nw * 64), smem, stream, p, nqt, Lp);
-      return hipGetLastError();
+  if (pl.family == PDM_ATTN_KV2 || pl.family == PDM_ATTN_KV3) {
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute((const void*)attention_kv_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute((const void*)attention_kv_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      attr = true;
     }
+    if (pl.family == PDM_ATTN_KV2) hipLaunchKernelGGL(attention_kv_kernel<2>, grid, block, smem, stream, p, nqt, Lp);
+    else hipLaunchKernelGGL(attention_kv_kernel<3>, grid, block, smem, stream, p, nqt, Lp);
+    return hipGetLastError();
   }
-  const int nqb = (nqt + 3) / 4;
-  const int nbh = p.B * p.H;
-  dim3 grid(((nbh + 7) / 8) * 8 * nqb), block(256);
   switch (p.Dh) {
     case 32: hipLaunchKernelGGL(attention_kernel<32>, grid, block, 0, stream, p, nqt); break;
     case 64: hipLaunchKernelGGL(attention_kernel<64>, grid, block, 0, stream, p, nqt); break;

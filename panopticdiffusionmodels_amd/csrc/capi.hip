@@ -991,6 +991,19 @@ int pdm_set_attention_algo(int algo) {
   return PDM_OK;
 }
 
+int pdm_attention_plan(int B, int L, int H, int Dh, int algo, int ncu, int* out6) {
+  if (!out6) return fail(PDM_ERR_ARG, "pdm_attention_plan: null output");
+  if (algo < 0 || algo > 16) return fail(PDM_ERR_ARG, "pdm_attention_plan: algo must be in [0, 16]");
+  if (ncu < 0) return fail(PDM_ERR_ARG, "pdm_attention_plan: ncu must be >= 0 (0: the default, 256)");
+  pdm::AttentionArgs a{};   // the shape checks of pdm_attention on dense, aligned (never dereferenced) operands
+  a.ldq = 3 * H * Dh; a.ldo = H * Dh; a.B = B; a.L = L; a.H = H; a.Dh = Dh;
+  PDM_CHECK(pdm::attention_check(a));
+  const pdm::AttentionPlan pl = pdm::attention_plan(B, L, H, Dh, algo, ncu ? ncu : 256);
+  out6[0] = pl.family; out6[1] = pl.waves; out6[2] = pl.tail1; out6[3] = pl.variant; out6[4] = pl.grid;
+  out6[5] = pl.lds_bytes;
+  return PDM_OK;
+}
+
 int pdm_device_arch(char* buf, int len) {
   int dev = 0;
   PDM_HIP(hipGetDevice(&dev));

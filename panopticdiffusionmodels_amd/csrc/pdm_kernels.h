@@ -155,6 +155,17 @@ struct AttentionArgs {
 const char* attention_check(const AttentionArgs& p);
 hipError_t attention_launch(const AttentionArgs& p, hipStream_t stream);
 void attention_set_algo(int algo);
+// Every decision of attention_launch as a pure function of the shape, the forced algo (pdm_set_attention_algo's
+// values) and the device's CU count; attention_launch switches on its result.  family: PDM_ATTN_* (include/pdm.h)
+struct AttentionPlan {
+  int family;
+  int waves;       // per workgroup
+  int tail1;       // the TK = 1 instantiation (last key block of 1..16 keys behind a full one)
+  int variant;     // 0 real kernel, 1 loads only, 2 math only (timing experiments)
+  int grid;        // workgroups
+  int lds_bytes;   // dynamic LDS
+};
+AttentionPlan attention_plan(int B, int L, int H, int Dh, int algo, int ncu);
 
 // Token assembly (libs/uvit.py:201-212, libs/uvit_t2i.py:382-409):
 // out[b, row] for the sequence [label?][time][context x n_ctx?][patches] + pos_embed, fp32.

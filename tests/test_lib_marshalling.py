@@ -68,7 +68,8 @@ def test_c_entry_call_sites_match_sigs():
 
 
 WRAPPERS = {n: getattr(_lib, n) for n in ("gemm", "rowstats", "gemm_ln", "mx_quantize_gpu", "gemm_ex", "gemm_pair",
-                                          "gemm_conv3x3", "gemm_batched", "layernorm", "attention", "lincomb",
+                                          "gemm_conv3x3", "gemm_batched", "layernorm", "attention", "attention_plan",
+                                          "lincomb",
                                           "stage_epilogue", "wgrad", "attention_backward", "layernorm_backward",
                                           "mx_quantize", "mx_dequantize", "mx_quantize_centred", "_gemm_args",
                                           "wgrad_gather", "colsum", "layernorm_backward_rows", "layernorm_rows",
@@ -165,6 +166,16 @@ def test_wrappers_marshal_against_fake_library(fake):
     qkv = torch.randn(2 * 17, 3 * 64).to(bf)
     _lib.attention(qkv, 2, 17, 1, 64)
     _lib.attention(qkv, 2, 17, 1, 64, q_log2=True)
+    # a preallocated output and a qkv view, each with its own row stride
+    wide_q, wide_o = torch.zeros(2 * 17 + 4, 3 * 64 + 8, dtype=bf), torch.zeros(2 * 17 + 4, 64 + 4, dtype=bf)
+    o = wide_o[2:36, :64]
+    assert _lib.attention(wide_q[2:36, :192], 2, 17, 1, 64, out=o) is o
+    assert _lib.attention(qkv, 2, 17, 1, 64, q_log2=True, out=o) is o
+    for bad in (torch.zeros(34, 64), torch.zeros(33, 64, dtype=bf), torch.zeros(34, 128, dtype=bf)[:, ::2],
+                torch.zeros(34, 65, dtype=bf)):
+        with pytest.raises(ValueError):
+            _lib.attention(qkv, 2, 17, 1, 64, out=bad)
+    assert _lib.attention_plan(2, 17, 1, 64).family == "streamed"   # the fake leaves out6 zeroed
     _lib.lincomb([torch.randn(8), torch.randn(8)], [1.0, 0.5])
     pre = torch.randn(4, 4, 8, 8)
     _lib.stage_epilogue(pre, 2, conv_w=torch.randn(4, 4, 3, 3), conv_b=torch.randn(4), cfg_scale=0.4,
@@ -217,7 +228,8 @@ def test_wrappers_marshal_against_fake_library(fake):
     p.disable()
     for name in ("pdm_gemm_bf16", "pdm_rowstats", "pdm_gemm_bf16_ln", "pdm_mx_quantize", "pdm_gemm", "pdm_gemm_pair",
                  "pdm_gemm_conv3x3_bf16", "pdm_gemm_batched_bf16", "pdm_layernorm", "pdm_attention",
-                 "pdm_attention_log2", "pdm_lincomb", "pdm_stage_epilogue", "pdm_wgrad", "pdm_attention_backward",
+                 "pdm_attention_log2", "pdm_attention_plan", "pdm_lincomb", "pdm_stage_epilogue", "pdm_wgrad",
+                 "pdm_attention_backward",
                  "pdm_layernorm_backward", "pdm_uvit_profile", "pdm_uvit_profile_read", "pdm_wgrad_gather",
                  "pdm_colsum", "pdm_layernorm_backward_rows", "pdm_layernorm_rows", "pdm_gelu_forward",
                  "pdm_gelu_backward", "pdm_lsimple", "pdm_conv3x3_backward", "pdm_head_forward", "pdm_head_backward",
