@@ -89,6 +89,24 @@ int pdm_set_attention_algo(int algo);
 #define PDM_ATTN_H72 6        /* head-resident Dh 72, one workgroup per head */
 #define PDM_ATTN_H72P 7       /* persistent head-resident Dh 72 */
 int pdm_attention_plan(int B, int L, int H, int Dh, int algo, int ncu, int* out6);
+/* GEMM kernel families (pdm_gemm_plan below, declared after pdm_gemm_args) */
+#define PDM_GEMM_128 0        /* 128 x 128 tile, 4 waves (any shape; the fallback) */
+#define PDM_GEMM_RING32 1     /* 256 x 256 tile, BK 32 x 4-stage ring (algo 2) */
+#define PDM_GEMM_RING64 2     /* 256 x 256 tile, BK 64 x 2-stage ring (algo 3) */
+#define PDM_GEMM_8P 3         /* 256 x 256 tile, 8-phase schedule (algo 4) */
+#define PDM_GEMM_8D 4         /* 256 x 256 tile, descriptor-addressed 8-phase (algo 5 / 6 / 7 = sched 0 / 1 / 2) */
+#define PDM_GEMM_8D_HN 5      /* the same on a 256 x 128 half-N tile (algo 8) */
+#define PDM_GEMM_8T 6         /* 512 x 128 tall tile (algo 9) */
+#define PDM_GEMM_8S 7         /* persistent 256 x 256 (algo 11), whole tiles or stream-K */
+#define PDM_GEMM_8S_MX 8      /* persistent with MXFP8 operands */
+#define PDM_GEMM_8G 9         /* persistent, two problems grouped (pdm_gemm_pair) */
+#define PDM_GEMM_MX 10        /* 256 x 256 tile with MXFP8 operands */
+#define PDM_GEMM_FAMILIES 11
+/* why a plan cannot be launched (pdm_gemm fails with PDM_ERR_HIP / invalid value there) */
+#define PDM_GEMM_ERR_FP8_RANGE 1   /* MXFP8 operand spanning >= 2 GiB */
+#define PDM_GEMM_ERR_NOSTORE 2     /* the no-store timing mode with conv, batch or operands >= 2 GiB */
+#define PDM_GEMM_ERR_GUARD 3       /* half-N / tall tile with N > 128, a batch (tall) or another epilogue than bf16 / fp32 */
+#define PDM_GEMM_ERR_EPI 4         /* the family has no instantiation with these template coordinates */
 
 /* ---- network handle: libs/uvit.py:138-230 UViT, libs/uvit_t2i.py:258-525 UViT (t2i) -------------- */
 typedef struct pdm_uvit pdm_uvit;
@@ -288,6 +306,27 @@ int pdm_gemm(const pdm_gemm_args* a, int epi, void* stream);
 int pdm_gemm_pair(const pdm_gemm_args* a, const pdm_gemm_args* b, int epi, void* stream);
 /* sizeof(pdm_gemm_args) as compiled into the library (binding layout check) */
 int pdm_gemm_args_size(void);
+/* What pdm_gemm (b == NULL) or pdm_gemm_pair (b != NULL) would launch, with no side effect.  The GEMM launcher, the
+ * pairing rule and the GroupNorm-partials rule take their decisions from this same function.  Nothing is dereferenced:
+ * the operand pointers of `a` / `b` count only by being null or not and by their low address bits, so made-up
+ * addresses serve.  `o` adds what pdm_gemm_args lacks and the policy; a negative policy field means this process's
+ * current value (pdm_set_gemm_algo / _sk / _tuning) -- for ncu and persist_ok that asks the device as the launcher
+ * does, so a caller without a GPU passes both.  out24 = {error (PDM_GEMM_ERR_*, 0 none), family (PDM_GEMM_*), template
+ * coordinates epi, conv, sched, mxo, sk, fp8, dual, grid x, grid y, block, dynamic LDS bytes, tiles_n, ntiles, nt0
+ * (grouped: the first problem's tiles), raster, split_m1 (> 0: rows [0, split_m1) and the rest are planned and launched
+ * separately; family is the first part's), row-stats post-pass, out2-copy post-pass, writes_gn (the epilogue writes
+ * GroupNorm partials, on every part of a split), gn_fusable (writes_gn and the partials' shape rule: what
+ * pdm_gemm_bf16_gn reports as fused), grouped (b != NULL and one launch takes both), row of the kernel table}.
+ * PDM_ERR_ARG for arguments pdm_gemm rejects or a null a / o / out24. */
+typedef struct pdm_gemm_plan_opts {
+  int convH, convW, convC, conv_up;   /* convC > 0: conv3x3 mode as pdm_gemm_conv3x3_bf16 (K = 9 convC, lda1 = convC) */
+  int batch;                          /* > 1: batched as pdm_gemm_batched_bf16 */
+  int act;                            /* GELU epilogue: 1 = quick GELU */
+  int gn_P;                           /* > 0: GroupNorm partials requested, gn_P rows per image */
+  int sk_attached;                    /* stream-K flag block and slab attached to the launch */
+  int algo, sk_mode, raster, dbg, mx_res_persist, ncu, persist_ok;   /* the policy */
+} pdm_gemm_plan_opts;
+int pdm_gemm_plan(const pdm_gemm_args* a, const pdm_gemm_args* b, int epi, const pdm_gemm_plan_opts* o, int* out24);
 /* Implicit-GEMM conv3x3 (stride 1, pad 1) on NHWC bf16 input [B, H>>up, W>>up, Cin] (up = 1: the nearest-x2
  * upsample of libs/autoencoder.py:35-50 folded into the addressing); Wt [N][9*Cin] in (ky, kx, ci) order;
  * output rows = output pixels (b, y, x), N channels (libs/autoencoder.py ResnetBlock conv1/conv2, Upsample.conv) */

@@ -102,8 +102,16 @@ class PdmGemmArgs(ctypes.Structure):
     ]
 
 
+class PdmGemmPlanOpts(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int) for n in (
+        "convH", "convW", "convC", "conv_up", "batch", "act", "gn_P", "sk_attached", "algo", "sk_mode", "raster", "dbg",
+        "mx_res_persist", "ncu", "persist_ok")]
+
+
 _SIGS = {
     "pdm_gemm_args_size": (ctypes.c_int, []),
+    "pdm_gemm_plan": (ctypes.c_int, [ctypes.POINTER(PdmGemmArgs), ctypes.POINTER(PdmGemmArgs), ctypes.c_int,
+                                     ctypes.POINTER(PdmGemmPlanOpts), ctypes.POINTER(ctypes.c_int)]),
     "pdm_last_error": (ctypes.c_char_p, []),
     "pdm_version": (ctypes.c_int, []),
     "pdm_device_arch": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_int]),
@@ -737,6 +745,71 @@ def attention_plan(B, L, H, Dh, algo=0, ncu=256):
     out = (ctypes.c_int * 6)()
     check(load().pdm_attention_plan(B, L, H, Dh, int(algo), int(ncu), out), "pdm_attention_plan")
     return AttentionPlan(ATTENTION_FAMILIES[out[0]], out[1], bool(out[2]), out[3], out[4], out[5])
+
+
+GEMM_FAMILIES = ("128", "ring32", "ring64", "8p", "8d", "8d_hn", "8t", "8s", "8s_mx", "8g", "mx")   # PDM_GEMM_*
+GEMM_PLAN_ERRORS = (None, "fp8_range", "nostore", "guard", "epi")                                  # PDM_GEMM_ERR_*
+GemmPlan = collections.namedtuple(
+    "GemmPlan", "error family epi conv sched mxo sk fp8 dual grid_x grid_y block lds_bytes tiles_n ntiles nt0 raster "
+                "split_m1 rowstats out2_copy writes_gn gn_fusable grouped kernel")
+
+
+def gemm_plan(g, epi, second=None, conv=None, batch=0, act=0, gn_P=0, sk_attached=False, algo=-1, sk_mode=-1,
+              raster=-1, dbg=-1, mx_res_persist=-1, ncu=-1, persist_ok=-1):
+    """What pdm_gemm(g, epi) -- with `second`, pdm_gemm_pair -- launches: GemmPlan(error name or None, family name,
+    the instantiation's template coordinates, launch geometry, row split, post-passes, writes_gn, gn_fusable, grouped,
+    kernel-table row).  g / second: PdmGemmArgs (`_gemm_args(...)` of tensors, or made-up addresses: nothing is
+    dereferenced).  conv = (H, W, Cin, up), batch, act, gn_P, sk_attached: what the struct lacks.  The policy fields
+    default to this process's current values; ncu / persist_ok then ask the device, so pass both without a GPU.  The
+    launcher, the pairing rule and the GroupNorm-partials rule decide with the same function."""
+    o = PdmGemmPlanOpts()
+    if conv is not None:
+        o.convH, o.convW, o.convC, o.conv_up = conv
+    o.batch, o.act, o.gn_P, o.sk_attached = int(batch), int(act), int(gn_P), int(bool(sk_attached))
+    o.algo, o.sk_mode, o.raster, o.dbg = int(algo), int(sk_mode), int(raster), int(dbg)
+    o.mx_res_persist, o.ncu, o.persist_ok = int(mx_res_persist), int(ncu), int(persist_ok)
+    out = (ctypes.c_int * 24)()
+    check(load().pdm_gemm_plan(ctypes.byref(g), ctypes.byref(second) if second is not None else None, int(epi),
+                               ctypes.byref(o), out), "pdm_gemm_plan")
+    v = list(out)
+    return GemmPlan(GEMM_PLAN_ERRORS[v[0]], GEMM_FAMILIES[v[1]] if v[1] >= 0 else None, *v[2:17], v[17],
+                    *(bool(x) for x in v[18:23]), v[23])
+
+
+def gemm_shape_args(M, N, K, epi, K1=None, copy=False, ln=False, stats=False, accumulate=False, fp8=False,
+                    out_fp8=False, gather=None, out2=None, conv_C=0):
+    """PdmGemmArgs of a GEMM on dense, aligned operands -- what the wrappers above pass for contiguous tensors -- on
+    stand-in addresses, for gemm_plan (which dereferences nothing).  K1 < K: the split-K second operand; copy: the
+    fp32 epilogue's bf16 copy; ln / stats: LayerNorm consumer / producer; out_fp8: the MXFP8 copy (alone on the bf16 /
+    GELU epilogues); gather = (rows_per_group, group_stride); out2 likewise; conv_C: a conv's input channels."""
+    g = PdmGemmArgs()
+    at = iter(range(1 << 20, 1 << 26, 1 << 20))
+    g.M, g.N, g.K, g.K1 = M, N, K, K if K1 is None else K1
+    g.A1, g.lda1, g.W = next(at), conv_C or g.K1, next(at)
+    if g.K1 < K:
+        g.A2, g.lda2 = next(at), K - g.K1
+    if epi == EPI_F32:
+        g.out_f32, g.ldr = next(at), N
+    if (epi != EPI_F32 and not (out_fp8 and epi != EPI_RES)) or copy:
+        g.out_bf16, g.ldo = next(at), N
+    g.accumulate = int(accumulate)
+    if accumulate and epi == EPI_RES:
+        g.res_in, g.ldri = g.out_bf16, N
+    if ln:
+        g.ln_stats, g.ln_colsum, g.ln_eps = next(at), next(at), 1e-5
+        g.ln_gcol = next(at) if fp8 else None
+    if stats:
+        g.stats_out = next(at)
+    if fp8:
+        g.fp8, g.a_scale, g.a_scale_ld, g.w_scale, g.w_scale_ld = 1, next(at), M, next(at), N
+    if out_fp8:
+        g.out_fp8, g.ldo8, g.out_scale, g.out_scale_ld = next(at), N, next(at), M
+    if gather:
+        g.a_rows_per_group, g.a_group_stride = gather
+    if out2:
+        g.out2, (g.out2_rows_per_group, g.out2_group_stride) = next(at), out2
+        g.stats_out2 = next(at) if stats else None
+    return g
 
 
 def attention(qkv, B, L, H, Dh, scale=None, q_log2=False, out=None):

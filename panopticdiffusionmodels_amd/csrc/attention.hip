@@ -1666,23 +1666,12 @@ AttentionPlan attention_plan(int B, int L, int H, int Dh, int algo, int ncu) {
   return {PDM_ATTN_STREAMED, 4, 0, 0, ((nbh + 7) / 8) * 8 * nqb, 0};
 }
 
-// compute units of the current device, asked once (the persistent kernels' grids); 256 if the runtime will not say
-static int attention_ncu() {
-  static const int ncu = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      return n;
-    return 256;
-  }();
-  return ncu;
-}
-
 hipError_t attention_launch(const AttentionArgs& args, hipStream_t stream) {
   AttentionArgs p = args;
   const int nqt = (p.L + 15) / 16;
   const int Lp = (p.L + 31) / 32 * 32;
   const int LV = (p.L + 7) / 8 * 8, L16 = (p.L + 15) / 16 * 16;
-  const AttentionPlan pl = attention_plan(p.B, p.L, p.H, p.Dh, g_attention_algo, attention_ncu());
+  const AttentionPlan pl = attention_plan(p.B, p.L, p.H, p.Dh, g_attention_algo, device_ncu());
   const dim3 grid(pl.grid), block(pl.waves * 64);
   const int smem = pl.lds_bytes;
   switch (pl.family) {

@@ -1438,6 +1438,53 @@ int pdm_gemm_pair(const pdm_gemm_args* ga, const pdm_gemm_args* gb, int epi, voi
 
 int pdm_gemm_args_size(void) { return (int)sizeof(pdm_gemm_args); }
 
+// the GemmArgs pdm_gemm builds, with the launch options pdm_gemm_args lacks; stand-in addresses (never dereferenced)
+// for the operands the options imply
+static pdm::GemmArgs to_plan_args(const pdm_gemm_args* g, const pdm_gemm_plan_opts* o) {
+  pdm::GemmArgs a = to_gemm_args(g);
+  void* const stand_in = (void*)(uintptr_t)4096;
+  if (o->convC > 0) {
+    a.conv = 1; a.convH = o->convH; a.convW = o->convW; a.convC = o->convC; a.conv_up = o->conv_up;
+    a.zero = (const bf16*)stand_in;
+  }
+  a.batch = o->batch;
+  a.act = o->act;
+  if (o->gn_P > 0) { a.gn_part = (double*)stand_in; a.gn_P = o->gn_P; a.gn_cpg = a.N / 32; }
+  if (o->sk_attached) { a.sk_flags = (unsigned*)stand_in; a.sk_slab = (float*)stand_in; }
+  return a;
+}
+
+int pdm_gemm_plan(const pdm_gemm_args* ga, const pdm_gemm_args* gb, int epi, const pdm_gemm_plan_opts* o, int* out24) {
+  if (!ga || !o || !out24) return fail(PDM_ERR_ARG, "pdm_gemm_plan: null argument");
+  if (o->algo > 11 || o->algo == 10 || (o->sk_mode > 2) || o->raster > 64)
+    return fail(PDM_ERR_ARG, "pdm_gemm_plan: algo must be 0..9 or 11, sk_mode 0..2, raster <= 64 (negative: current)");
+  const pdm::GemmArgs a = to_plan_args(ga, o);
+  PDM_CHECK(pdm::gemm_check(a, epi));
+  pdm::GemmPolicy pol = pdm::gemm_policy(o->ncu > 0 ? o->ncu : -1, o->persist_ok);
+  if (o->algo >= 0) pol.algo = o->algo;
+  if (o->sk_mode >= 0) pol.sk = o->sk_mode;
+  if (o->raster >= 0) pol.raster = o->raster;
+  if (o->dbg >= 0) pol.dbg = o->dbg;
+  if (o->mx_res_persist >= 0) pol.mx_res_persist = o->mx_res_persist;
+  pdm::GemmPlan pl{};
+  bool grouped = false;
+  if (gb) {
+    const pdm::GemmArgs b = to_plan_args(gb, o);
+    PDM_CHECK(pdm::gemm_check(b, epi));
+    grouped = pdm::gemm_plan_pair(a, b, epi, pol, &pl);
+  }
+  if (!grouped) {
+    pdm::GemmArgs one = a;
+    if (gb) one.sk_flags = nullptr, one.sk_slab = nullptr;   // pdm_gemm_pair: one flag block serves one launch
+    pl = pdm::gemm_plan(one, epi, pol);
+  }
+  const int v[24] = {pl.error, pl.family, pl.epi, pl.conv, pl.sched, pl.mxo, pl.sk, pl.fp8, pl.dual, pl.grid_x, pl.grid_y,
+                     pl.block, pl.lds_bytes, pl.tiles_n, pl.ntiles, pl.nt0, pl.raster, pl.split_m1, pl.rowstats,
+                     pl.out2_copy, pl.writes_gn, pdm::gemm_gn_fusable(a, epi, pol), grouped, pl.kernel};
+  for (int i = 0; i < 24; ++i) out24[i] = v[i];
+  return PDM_OK;
+}
+
 int pdm_gemm_conv3x3_bf16(const void* in, int B, int H, int W, int Cin, int up, const void* Wt, const float* bias,
                           int N, int epi, void* out_bf16, float* out_f32, int accumulate, void* stream) {
   static bf16* zero = nullptr;   // zero page for the tile policies that address padded taps explicitly

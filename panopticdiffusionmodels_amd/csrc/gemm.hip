@@ -15,6 +15,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "../../include/pdm.h"
 #include "pdm_common.h"
 #include "pdm_kernels.h"
 
@@ -2998,254 +2999,84 @@ int gemm_sk_stats(unsigned long long* out) {   // reads and clears the device co
 void gemm_set_tuning(int raster, int dbg_tile0) { g_gemm_raster = raster; g_gemm_dbg = dbg_tile0; }  // 0 auto, 1 = 128x128, 2 = 256x256 BK32 x4 ring, 3 = 256x256 BK64 x2, 4 = 256x256 8-phase
 void gemm_set_algo(int algo) { g_gemm_algo = algo; }
 
-template <int BK, int NS>
-static hipError_t launch256(const GemmArgs& p, int epi, hipStream_t stream) {
-  constexpr int SMEM = (BM2 + BN2) * BK * 2 * NS + EPI_LDS_EXTRA;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI_BF16, BK, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI_GELU, BK, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm256_kernel<EPI_F32, BK, NS>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
-  const int tn = (p.N + BN2 - 1) / BN2, tm = (p.M + BM2 - 1) / BM2;
-  const int nwg = tm * tn;
-  dim3 grid(nwg, p.batch > 1 ? p.batch : 1), block(512);
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((gemm256_kernel<EPI_BF16, BK, NS>), grid, block, SMEM, stream, p, tn, nwg); break;
-    case EPI_GELU: hipLaunchKernelGGL((gemm256_kernel<EPI_GELU, BK, NS>), grid, block, SMEM, stream, p, tn, nwg); break;
-    default: hipLaunchKernelGGL((gemm256_kernel<EPI_F32, BK, NS>), grid, block, SMEM, stream, p, tn, nwg); break;
-  }
-  return hipGetLastError();
-}
-
-template <int CONV>
-static hipError_t launch8p(const GemmArgs& p, int epi, hipStream_t stream) {
-  constexpr int SMEM = 2 * 4 * 128 * 128 + EPI_LDS_EXTRA;   // 128 KiB ring + LN row stats
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm8p_kernel<EPI_BF16, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8p_kernel<EPI_GELU, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8p_kernel<EPI_F32, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
-  const int tn = (p.N + BN2 - 1) / BN2, tm = (p.M + BM2 - 1) / BM2;
-  const int nwg = tm * tn;
-  dim3 grid(nwg, p.batch > 1 ? p.batch : 1), block(512);
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((gemm8p_kernel<EPI_BF16, CONV>), grid, block, SMEM, stream, p, tn, nwg); break;
-    case EPI_GELU: hipLaunchKernelGGL((gemm8p_kernel<EPI_GELU, CONV>), grid, block, SMEM, stream, p, tn, nwg); break;
-    default: hipLaunchKernelGGL((gemm8p_kernel<EPI_F32, CONV>), grid, block, SMEM, stream, p, tn, nwg); break;
-  }
-  return hipGetLastError();
-}
-
-template <int CONV>
-static hipError_t launch8t(const GemmArgs& p, int epi, hipStream_t stream) {
-  constexpr int SMEM = 2 * 5 * 128 * 128;   // 160 KiB
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm8t_kernel<EPI_BF16, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8t_kernel<EPI_F32, CONV>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
-  if (p.N > 128 || p.batch > 1 || (epi != EPI_BF16 && epi != EPI_F32)) return hipErrorInvalidValue;
-  const int nwg = (p.M + 511) / 512;
-  if (epi == EPI_BF16) hipLaunchKernelGGL((gemm8t_kernel<EPI_BF16, CONV>), dim3(nwg), dim3(512), SMEM, stream, p, nwg);
-  else hipLaunchKernelGGL((gemm8t_kernel<EPI_F32, CONV>), dim3(nwg), dim3(512), SMEM, stream, p, nwg);
-  return hipGetLastError();
-}
-
-template <int CONV>
-static hipError_t launch8d_hn(const GemmArgs& p, int epi, hipStream_t stream) {
-  constexpr int SMEM = 2 * 4 * 128 * 128 + EPI_LDS_EXTRA + COL_LDS_BYTES;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm8d_kernel<EPI_BF16, CONV, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8d_kernel<EPI_F32, CONV, 2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
-  if (p.N > 128 || (epi != EPI_BF16 && epi != EPI_F32)) return hipErrorInvalidValue;
-  const int nwg = (p.M + BM2 - 1) / BM2;
-  dim3 grid(nwg, p.batch > 1 ? p.batch : 1), block(512);
-  if (epi == EPI_BF16) hipLaunchKernelGGL((gemm8d_kernel<EPI_BF16, CONV, 2, 1>), grid, block, SMEM, stream, p, 1, nwg);
-  else hipLaunchKernelGGL((gemm8d_kernel<EPI_F32, CONV, 2, 1>), grid, block, SMEM, stream, p, 1, nwg);
-  return hipGetLastError();
-}
-
-template <int CONV, int SCHED>
-static hipError_t launch8d(const GemmArgs& p, int epi, hipStream_t stream) {
-  constexpr int SMEM = 2 * 4 * 128 * 128 + EPI_LDS_EXTRA + COL_LDS_BYTES;   // ring + LN rows + bias / colsum
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm8d_kernel<EPI_BF16, CONV, SCHED>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8d_kernel<EPI_GELU, CONV, SCHED>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8d_kernel<EPI_F32, CONV, SCHED>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    if constexpr (!CONV && SCHED == 2)
-      (void)hipFuncSetAttribute((const void*)gemm8d_kernel<EPI_RES, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-    attr_set = true;
-  }
-  const int tn = (p.N + BN2 - 1) / BN2, tm = (p.M + BM2 - 1) / BM2;
-  const int nwg = tm * tn;
-  dim3 grid(nwg, p.batch > 1 ? p.batch : 1), block(512);
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((gemm8d_kernel<EPI_BF16, CONV, SCHED>), grid, block, SMEM, stream, p, tn, nwg); break;
-    case EPI_GELU: hipLaunchKernelGGL((gemm8d_kernel<EPI_GELU, CONV, SCHED>), grid, block, SMEM, stream, p, tn, nwg); break;
-    case EPI_RES:
-      if constexpr (!CONV && SCHED == 2) {
-        hipLaunchKernelGGL((gemm8d_kernel<EPI_RES, 0, 2>), grid, block, SMEM, stream, p, tn, nwg);
-        break;
-      }
-      return hipErrorInvalidValue;
-    default: hipLaunchKernelGGL((gemm8d_kernel<EPI_F32, CONV, SCHED>), grid, block, SMEM, stream, p, tn, nwg); break;
-  }
-  return hipGetLastError();
-}
-
-static int g_num_cus = 0;
-// q / nt0: the grouped launch's second problem and the first one's tile count (q = p, nt0 = all tiles: one problem)
-static hipError_t launch8s(const GemmArgs& p, int epi, hipStream_t stream, const GemmArgs* p2 = nullptr) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_RES>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_GELU, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16, 0, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_GELU, 0, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_RES, 0, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16, 1, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_GELU, 1, 0, 0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
-      g_num_cus = n;
-    else
-      g_num_cus = 256;
-    attr_set = true;
-  }
-  const int tn = (p.N + BN2 - 1) / BN2, tm = (p.M + BM2 - 1) / BM2;
-  const int nt0 = tm * tn;
-  const int ntiles = nt0 + (p2 ? (p2->M + BM2 - 1) / BM2 * tn : 0);
-  const GemmArgs& q = p2 ? *p2 : p;
-  const int grid = ntiles < g_num_cus ? ntiles : g_num_cus;
-  // stream-K where the last wave of tiles leaves CUs idle and every workgroup's share is >= nk + 4 K-steps (so each
-  // tile has at most two pieces and the consumer's tail normally finds its flag up, gemm8s_body)
-  bool sk = false;
-  if (!p2 && p.sk_flags && p.sk_slab && g_gemm_sk && ntiles > grid && grid <= SK_FLAG_WORDS && grid >= 8 &&
-      ntiles % grid) {
-    const int nk = p.K / 64, gx = (grid + 7) / 8, tmin = ntiles / 8;
-    const int waves = (ntiles + grid - 1) / grid;
-    const double fill = (double)ntiles / ((double)waves * grid);
-    sk = (long long)tmin * nk >= (long long)gx * (nk + 4) && (g_gemm_sk == 2 || fill < 0.97);
-  }
-  if (sk) {
-    ++g_sk_launches;
-    static bool attr_sk = false;
-    if (!attr_sk) {
-      (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_GELU, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_RES, 0, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_GELU, 1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      attr_sk = true;
+// ------------------------------------------------------------------------------------------------
+// Every instantiated GEMM kernel, by family and template coordinates (GemmPlan's): the plan finds its row here, the
+// launcher sets the dynamic-LDS attribute of a family's rows at the family's first launch, persist_kernels_ok walks
+// the persistent families' rows.
+namespace {
+struct KernelRow {
+  int family, epi, conv, sched, mxo, sk, fp8, dual;
+  const void* fn;
+  int lds;
+};
+constexpr int SMEM_RING = (BM2 + BN2) * 32 * 2 * 4 + EPI_LDS_EXTRA;          // BK 32 x 4 = BK 64 x 2: 128 KiB + LN row stats
+constexpr int SMEM_8P = 2 * 4 * 128 * 128 + EPI_LDS_EXTRA;                   // 128 KiB ring + LN row stats
+constexpr int SMEM_8D = 2 * 4 * 128 * 128 + EPI_LDS_EXTRA + COL_LDS_BYTES;   // ring + LN rows + bias / colsum
+constexpr int SMEM_8T = 2 * 5 * 128 * 128;                                   // 160 KiB
+#define R128(E) {PDM_GEMM_128, E, 0, 0, 0, 0, 0, 0, (const void*)gemm_bf16_kernel<E>, SMEM_BYTES}
+#define RRING(F, E, BK_, NS) {F, E, 0, 0, 0, 0, 0, 0, (const void*)gemm256_kernel<E, BK_, NS>, SMEM_RING}
+#define R8P(E, C) {PDM_GEMM_8P, E, C, 0, 0, 0, 0, 0, (const void*)gemm8p_kernel<E, C>, SMEM_8P}
+#define R8D(E, C, S) {PDM_GEMM_8D, E, C, S, 0, 0, 0, 0, (const void*)gemm8d_kernel<E, C, S>, SMEM_8D}
+#define R8DH(E, C) {PDM_GEMM_8D_HN, E, C, 2, 0, 0, 0, 0, (const void*)gemm8d_kernel<E, C, 2, 1>, SMEM_8D}
+#define R8T(E, C) {PDM_GEMM_8T, E, C, 0, 0, 0, 0, 0, (const void*)gemm8t_kernel<E, C>, SMEM_8T}
+#define R8S(E, MXO, SK, DUAL) {PDM_GEMM_8S, E, 0, 0, MXO, SK, 0, DUAL, (const void*)gemm8s_kernel<E, MXO, SK, 0, DUAL>, S_SMEM}
+#define R8SMX(E) {PDM_GEMM_8S_MX, E, 0, 0, 0, 0, 1, 0, (const void*)gemm8s_kernel<E, 0, 0, 1, 0>, S_SMEM_MX}
+#define R8G(E, DUAL) {PDM_GEMM_8G, E, 0, 0, 0, 0, 0, DUAL, (const void*)gemm8g_kernel<E, DUAL>, S_SMEM}
+#define RMX(E) {PDM_GEMM_MX, E, 0, 0, 0, 0, 1, 0, (const void*)gemm_mx_kernel<E>, MX_SMEM}
+const KernelRow g_kernels[] = {
+    R128(EPI_BF16), R128(EPI_GELU), R128(EPI_F32), R128(EPI_RES),
+    RRING(PDM_GEMM_RING32, EPI_BF16, 32, 4), RRING(PDM_GEMM_RING32, EPI_GELU, 32, 4), RRING(PDM_GEMM_RING32, EPI_F32, 32, 4),
+    RRING(PDM_GEMM_RING64, EPI_BF16, 64, 2), RRING(PDM_GEMM_RING64, EPI_GELU, 64, 2), RRING(PDM_GEMM_RING64, EPI_F32, 64, 2),
+    R8P(EPI_BF16, 0), R8P(EPI_GELU, 0), R8P(EPI_F32, 0), R8P(EPI_BF16, 1), R8P(EPI_GELU, 1), R8P(EPI_F32, 1),
+    R8D(EPI_BF16, 0, 0), R8D(EPI_GELU, 0, 0), R8D(EPI_F32, 0, 0), R8D(EPI_BF16, 1, 0), R8D(EPI_GELU, 1, 0), R8D(EPI_F32, 1, 0),
+    R8D(EPI_BF16, 0, 1), R8D(EPI_GELU, 0, 1), R8D(EPI_F32, 0, 1), R8D(EPI_BF16, 1, 1), R8D(EPI_GELU, 1, 1), R8D(EPI_F32, 1, 1),
+    R8D(EPI_BF16, 0, 2), R8D(EPI_GELU, 0, 2), R8D(EPI_F32, 0, 2), R8D(EPI_BF16, 1, 2), R8D(EPI_GELU, 1, 2), R8D(EPI_F32, 1, 2),
+    R8D(EPI_RES, 0, 2),   // the residual epilogue exists in the default schedule only
+    R8DH(EPI_BF16, 0), R8DH(EPI_F32, 0), R8DH(EPI_BF16, 1), R8DH(EPI_F32, 1),
+    R8T(EPI_BF16, 0), R8T(EPI_F32, 0), R8T(EPI_BF16, 1), R8T(EPI_F32, 1),
+    // persistent: the split-K second A operand (skip_linear's concat) needs the DUAL refill path, every other Linear
+    // takes DUAL = 0; MXO = the MXFP8 copy as the only output; stream-K (SK) comes with DUAL = 1 only
+    R8S(EPI_BF16, 0, 0, 1), R8S(EPI_GELU, 0, 0, 1), R8S(EPI_RES, 0, 0, 1), R8S(EPI_BF16, 1, 0, 1), R8S(EPI_GELU, 1, 0, 1),
+    R8S(EPI_BF16, 0, 0, 0), R8S(EPI_GELU, 0, 0, 0), R8S(EPI_RES, 0, 0, 0), R8S(EPI_BF16, 1, 0, 0), R8S(EPI_GELU, 1, 0, 0),
+    R8S(EPI_BF16, 0, 1, 1), R8S(EPI_GELU, 0, 1, 1), R8S(EPI_RES, 0, 1, 1), R8S(EPI_BF16, 1, 1, 1), R8S(EPI_GELU, 1, 1, 1),
+    R8SMX(EPI_BF16), R8SMX(EPI_RES),
+    R8G(EPI_BF16, 1), R8G(EPI_GELU, 1), R8G(EPI_RES, 1), R8G(EPI_BF16, 0), R8G(EPI_GELU, 0), R8G(EPI_RES, 0),
+    RMX(EPI_BF16), RMX(EPI_GELU), RMX(EPI_F32), RMX(EPI_RES),
+};
+#undef R128
+#undef RRING
+#undef R8P
+#undef R8D
+#undef R8DH
+#undef R8T
+#undef R8S
+#undef R8SMX
+#undef R8G
+#undef RMX
+constexpr int N_KERNELS = sizeof(g_kernels) / sizeof(g_kernels[0]);
+struct FamilyRows {   // [begin[f], begin[f + 1]): the rows of family f (the table is sorted by family)
+  int begin[PDM_GEMM_FAMILIES + 1];
+  FamilyRows() {
+    for (int f = 0, i = 0; f <= PDM_GEMM_FAMILIES; ++f) {
+      while (i < N_KERNELS && g_kernels[i].family < f) ++i;
+      begin[f] = i;
     }
-    if (p.out_fp8) {
-      if (epi == EPI_BF16) hipLaunchKernelGGL((gemm8s_kernel<EPI_BF16, 1, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      else if (epi == EPI_GELU) hipLaunchKernelGGL((gemm8s_kernel<EPI_GELU, 1, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      else return hipErrorInvalidValue;
-      return hipGetLastError();
-    }
-    switch (epi) {
-      case EPI_BF16: hipLaunchKernelGGL((gemm8s_kernel<EPI_BF16, 0, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles); break;
-      case EPI_GELU: hipLaunchKernelGGL((gemm8s_kernel<EPI_GELU, 0, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles); break;
-      case EPI_RES: hipLaunchKernelGGL((gemm8s_kernel<EPI_RES, 0, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles); break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
   }
-  // the split-K second A operand (skip_linear's concat) needs the DUAL refill path; every other Linear takes DUAL = 0
-  const bool dual = p.A2 && p.K1 < p.K;
-  if (p.out_fp8) {   // fits_8s: bf16 / GELU with the MXFP8 copy as the only output
-    if (epi == EPI_BF16 && dual) hipLaunchKernelGGL((gemm8s_kernel<EPI_BF16, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-    else if (epi == EPI_BF16) hipLaunchKernelGGL((gemm8s_kernel<EPI_BF16, 1, 0, 0, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-    else if (epi == EPI_GELU && dual) hipLaunchKernelGGL((gemm8s_kernel<EPI_GELU, 1>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-    else if (epi == EPI_GELU) hipLaunchKernelGGL((gemm8s_kernel<EPI_GELU, 1, 0, 0, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-    else return hipErrorInvalidValue;
-    return hipGetLastError();
-  }
-  if (p2) {
-    static bool attr_g = false;
-    if (!attr_g) {
-      (void)hipFuncSetAttribute((const void*)gemm8g_kernel<EPI_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8g_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8g_kernel<EPI_RES>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8g_kernel<EPI_BF16, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8g_kernel<EPI_GELU, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      (void)hipFuncSetAttribute((const void*)gemm8g_kernel<EPI_RES, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, S_SMEM);
-      attr_g = true;
-    }
-    // both problems share A2's presence and K1 (gemm_pair_groups)
-    switch (epi) {
-      case EPI_BF16:
-        if (dual) hipLaunchKernelGGL(gemm8g_kernel<EPI_BF16>, dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles, view_of(q), nt0);
-        else hipLaunchKernelGGL((gemm8g_kernel<EPI_BF16, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles, view_of(q), nt0);
-        break;
-      case EPI_GELU:
-        if (dual) hipLaunchKernelGGL(gemm8g_kernel<EPI_GELU>, dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles, view_of(q), nt0);
-        else hipLaunchKernelGGL((gemm8g_kernel<EPI_GELU, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles, view_of(q), nt0);
-        break;
-      case EPI_RES:
-        if (dual) hipLaunchKernelGGL(gemm8g_kernel<EPI_RES>, dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles, view_of(q), nt0);
-        else hipLaunchKernelGGL((gemm8g_kernel<EPI_RES, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles, view_of(q), nt0);
-        break;
-      default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  switch (epi) {
-    case EPI_BF16:
-      if (dual) hipLaunchKernelGGL(gemm8s_kernel<EPI_BF16>, dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      else hipLaunchKernelGGL((gemm8s_kernel<EPI_BF16, 0, 0, 0, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      break;
-    case EPI_GELU:
-      if (dual) hipLaunchKernelGGL(gemm8s_kernel<EPI_GELU>, dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      else hipLaunchKernelGGL((gemm8s_kernel<EPI_GELU, 0, 0, 0, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      break;
-    case EPI_RES:
-      if (dual) hipLaunchKernelGGL(gemm8s_kernel<EPI_RES>, dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      else hipLaunchKernelGGL((gemm8s_kernel<EPI_RES, 0, 0, 0, 0>), dim3(grid), dim3(512), S_SMEM, stream, p, tn, ntiles);
-      break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
+};
+const FamilyRows g_family_rows;
+bool persistent_family(int f) { return f == PDM_GEMM_8S || f == PDM_GEMM_8S_MX || f == PDM_GEMM_8G; }
+}  // namespace
 
-// the persistent kernel's preconditions (epilogues, no conv / batch / gather / MXFP8 operands, K >= 256, one A
-// stride, buffer extents); an MXFP8 output only as the sole output of a bf16 / GELU epilogue (gemm_check has
-// validated its shape: N % 32, ldo8 % 16, out_scale_ld >= M)
 // The persistent kernel counts its VMEM ops by hand (the ring's vmcnt waits): a register spill would add scratch
 // traffic it does not expect, so every instantiation is checked once for a private segment; with one, the
 // persistent policy is off (whole-tile algo 7 instead) and the library says so on stderr.
 static bool persist_kernels_ok() {
   static int ok = -1;
   if (ok < 0) {
-    const void* fns[] = {(const void*)gemm8s_kernel<EPI_BF16>, (const void*)gemm8s_kernel<EPI_GELU>,
-                         (const void*)gemm8s_kernel<EPI_RES>, (const void*)gemm8s_kernel<EPI_BF16, 1>,
-                         (const void*)gemm8s_kernel<EPI_GELU, 1>, (const void*)gemm8s_kernel<EPI_BF16, 0, 1>,
-                         (const void*)gemm8s_kernel<EPI_GELU, 0, 1>, (const void*)gemm8s_kernel<EPI_RES, 0, 1>,
-                         (const void*)gemm8s_kernel<EPI_BF16, 1, 1>, (const void*)gemm8s_kernel<EPI_GELU, 1, 1>,
-                         (const void*)gemm8g_kernel<EPI_BF16>, (const void*)gemm8g_kernel<EPI_GELU>,
-                         (const void*)gemm8g_kernel<EPI_RES>, (const void*)gemm8s_kernel<EPI_BF16, 0, 0, 1, 0>,
-                         (const void*)gemm8s_kernel<EPI_RES, 0, 0, 1, 0>, (const void*)gemm8s_kernel<EPI_BF16, 0, 0, 0, 0>,
-                         (const void*)gemm8s_kernel<EPI_GELU, 0, 0, 0, 0>, (const void*)gemm8s_kernel<EPI_RES, 0, 0, 0, 0>,
-                         (const void*)gemm8s_kernel<EPI_BF16, 1, 0, 0, 0>, (const void*)gemm8s_kernel<EPI_GELU, 1, 0, 0, 0>,
-                         (const void*)gemm8g_kernel<EPI_BF16, 0>, (const void*)gemm8g_kernel<EPI_GELU, 0>,
-                         (const void*)gemm8g_kernel<EPI_RES, 0>};
     ok = 1;
-    for (const void* f : fns) {
+    for (const KernelRow& k : g_kernels) {
       hipFuncAttributes at{};
-      if (hipFuncGetAttributes(&at, f) != hipSuccess) continue;   // no device: the launch itself will fail
+      if (!persistent_family(k.family) || hipFuncGetAttributes(&at, k.fn) != hipSuccess) continue;   // no device: the launch itself will fail
       if (at.localSizeBytes > 0) ok = 0;
     }
     if (!ok) fprintf(stderr, "libpdm: a persistent GEMM instantiation uses scratch (register spill); using algo 7\n");
@@ -3253,90 +3084,9 @@ static bool persist_kernels_ok() {
   return ok == 1;
 }
 
-static bool fits_8s(const GemmArgs& p, int epi) {
-  const long long lim = 0x7fffffffLL;
-  if (!persist_kernels_ok()) return false;
-  if (epi != EPI_BF16 && epi != EPI_GELU && epi != EPI_RES) return false;
-  if (p.conv || p.batch > 1 || p.a_rows_per_group > 0 || p.fp8 || p.mx_center || p.out2) return false;
-  if (p.out_fp8) {
-    if (epi == EPI_RES || p.out_bf16 || !p.out_scale || p.N % 32 || p.ldo8 % 16 || p.out_scale_ld < p.M) return false;
-    if ((long long)p.M * p.ldo8 >= lim || (long long)((p.N + 127) >> 7) * p.out_scale_ld * 4 >= lim) return false;
-    if (epi == EPI_GELU && p.act) return false;
-    if (p.K < 256 || (p.A2 && p.K1 < p.K && p.lda2 != p.lda1) || (p.ln_stats && p.ln_ld > 8)) return false;
-    if (p.dbg_tile0 & 15) return false;
-    return fits_rsrc(p);
-  }
-  if (!p.out_bf16) return false;
-  if (epi == EPI_GELU && p.act) return false;
-  if (p.K < 256 || (p.A2 && p.K1 < p.K && p.lda2 != p.lda1) || p.N % 8 || p.ldo % 8 || ((uintptr_t)p.out_bf16 & 15) || (p.ln_stats && p.ln_ld > 8)) return false;
-  if ((long long)p.M * p.ldo * 2 >= lim) return false;
-  if (epi == EPI_RES && p.accumulate && (p.ldri % 8 || ((uintptr_t)p.res_in & 15) || (long long)p.M * p.ldri * 2 >= lim))
-    return false;
-  if (p.stats_out && (long long)p.M * p.stats_ld * 8 >= lim) return false;
-  if (p.dbg_tile0 & 15) return false;   // gemm8d's timing modes
-  return fits_rsrc(p);
-}
-
-// the persistent kernel's MXFP8-operand form (gemm8s_kernel<EPI, 0, 0, 1>): the bf16 epilogue with or without the
-// (centred) LayerNorm consumer -- the U-ViT-H/4 qkv, algo 11 only -- and the bf16-residual epilogue without an MXFP8
-// output copy -- the H/4 proj in 'fp8' mode (its x feeds the bf16 fc1), automatic where g_mx_res_persist allows
-static bool fits_8s_mx(const GemmArgs& p, int epi) {
-  const long long lim = 0x7fffffffLL;
-  if (!persist_kernels_ok()) return false;
-  if ((epi != EPI_BF16 && epi != EPI_RES) || !p.fp8 || p.out_fp8 || p.mx_center || p.A2 || p.K1 != p.K || p.conv ||
-      p.batch > 1 || p.a_rows_per_group > 0 || p.out2)
-    return false;
-  if (!p.out_bf16 || p.N % 8 || p.ldo % 8 || ((uintptr_t)p.out_bf16 & 15) || p.K % 128 || p.K < 512) return false;
-  if (p.ln_stats && p.ln_ld > 8) return false;
-  if ((long long)p.M * p.ldo * 2 >= lim || (p.dbg_tile0 & 15)) return false;
-  if (epi == EPI_RES && p.accumulate && (p.ldri % 8 || ((uintptr_t)p.res_in & 15) || (long long)p.M * p.ldri * 2 >= lim))
-    return false;
-  if (p.stats_out && (long long)p.M * p.stats_ld * 8 >= lim) return false;
-  return fits_rsrc(p);
-}
-
-static hipError_t launch8s_mx(const GemmArgs& p, int epi, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_BF16, 0, 0, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              S_SMEM_MX);
-    (void)hipFuncSetAttribute((const void*)gemm8s_kernel<EPI_RES, 0, 0, 1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              S_SMEM_MX);
-    attr_set = true;
-  }
-  if (g_num_cus == 0) {   // as launch8s
-    int dev = 0, n = 0;
-    g_num_cus = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-  }
-  const int tn = (p.N + BN2 - 1) / BN2, tm = (p.M + BM2 - 1) / BM2;
-  const int ntiles = tm * tn;
-  const int grid = ntiles < g_num_cus ? ntiles : g_num_cus;
-  if (epi == EPI_RES)
-    hipLaunchKernelGGL((gemm8s_kernel<EPI_RES, 0, 0, 1, 0>), dim3(grid), dim3(512), S_SMEM_MX, stream, p, tn, ntiles);
-  else
-    hipLaunchKernelGGL((gemm8s_kernel<EPI_BF16, 0, 0, 1, 0>), dim3(grid), dim3(512), S_SMEM_MX, stream, p, tn, ntiles);
-  return hipGetLastError();
-}
-
-static hipError_t launch_mx(const GemmArgs& p, int epi, hipStream_t stream) {
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_mx_kernel<EPI_BF16>, hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm_mx_kernel<EPI_GELU>, hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm_mx_kernel<EPI_F32>, hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-    (void)hipFuncSetAttribute((const void*)gemm_mx_kernel<EPI_RES>, hipFuncAttributeMaxDynamicSharedMemorySize, MX_SMEM);
-    attr_set = true;
-  }
-  const int tn = (p.N + BN2 - 1) / BN2, tm = (p.M + BM2 - 1) / BM2;
-  const int nwg = tm * tn;
-  dim3 grid(nwg), block(512);
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL(gemm_mx_kernel<EPI_BF16>, grid, block, MX_SMEM, stream, p, tn, nwg); break;
-    case EPI_GELU: hipLaunchKernelGGL(gemm_mx_kernel<EPI_GELU>, grid, block, MX_SMEM, stream, p, tn, nwg); break;
-    case EPI_RES: hipLaunchKernelGGL(gemm_mx_kernel<EPI_RES>, grid, block, MX_SMEM, stream, p, tn, nwg); break;
-    default: hipLaunchKernelGGL(gemm_mx_kernel<EPI_F32>, grid, block, MX_SMEM, stream, p, tn, nwg); break;
-  }
-  return hipGetLastError();
+GemmPolicy gemm_policy(int ncu, int persist_ok) {
+  return {g_gemm_algo, g_gemm_sk, g_gemm_raster, g_gemm_dbg, g_mx_res_persist, ncu >= 0 ? ncu : device_ncu(),
+          persist_ok >= 0 ? persist_ok : persist_kernels_ok()};
 }
 
 // The descriptor-addressed kernel needs every operand byte offset below 2^31 (32-bit per-lane offsets).
@@ -3354,61 +3104,153 @@ static bool fits_rsrc(const GemmArgs& p) {
          (!p.conv || (p.convW <= 512 && p.convH <= 512 && p.M / (p.convH * p.convW) < 8192));   // conv_off's packing
 }
 
-// the second residual output of a launch whose kernel has no out2 store (the 128 tile, a split launch): the rows
-// (and partials) copied from out_bf16 / stats_out after it, as 4-byte words
-static hipError_t out2_copy(const GemmArgs& p, hipStream_t stream) {
-  return rowcopy_launch(reinterpret_cast<float*>(p.out2), p.ldo / 2, reinterpret_cast<const float*>(p.out_bf16),
-                        p.ldo / 2, p.M, p.N / 2, p.out2_rpg, p.out2_gs, p.out2_rpg, stream, p.stats_out2,
-                        p.stats_ld * 2, p.stats_out, p.stats_ld * 2, p.stats_out2 ? p.stats_ld * 2 : 0);
+// What both persistent forms (bf16 operands, fits_8s; MXFP8 operands, fits_8s_mx) ask: no spilling instantiation,
+// no conv / batch / gather / second output / centred MXFP8 copy, LayerNorm partials of <= 8 groups, no timing mode,
+// buffer extents
+static bool fits_persist(const GemmArgs& p, const GemmPolicy& pol) {
+  if (!pol.persist_ok) return false;
+  if (p.conv || p.batch > 1 || p.a_rows_per_group > 0 || p.mx_center || p.out2) return false;
+  if ((p.ln_stats && p.ln_ld > 8) || (pol.dbg & 15)) return false;   // dbg: gemm8d's timing modes
+  return fits_rsrc(p);
 }
-
-bool gemm_pair_groups(const GemmArgs& p, const GemmArgs& q, int epi) {
-  const bool algo_ok = g_gemm_algo == 0 || g_gemm_algo == 11;
-  const bool same = p.N == q.N && p.K == q.K && p.K1 == q.K1 && p.lda1 == q.lda1 && p.ldw == q.ldw && p.ldo == q.ldo &&
-                    p.ldri == q.ldri && p.accumulate == q.accumulate && p.stats_ld == q.stats_ld && p.ln_ld == q.ln_ld &&
-                    p.ln_D == q.ln_D && p.ln_eps == q.ln_eps && !p.bias == !q.bias && !p.ln_stats == !q.ln_stats &&
-                    !p.stats_out == !q.stats_out && !p.A2 == !q.A2 && (!p.A2 || p.lda2 == q.lda2) && !p.out_fp8 && !q.out_fp8;
-  // grouped only where each GEMM alone would take the persistent kernel (gemm_launch's rule), so a problem's
-  // arithmetic -- and the sampler's batch invariance -- does not depend on the other problem's rows
-  return algo_ok && same && p.M >= 4096 && q.M >= 4096 && p.N >= 256 && fits_8s(p, epi) && fits_8s(q, epi);
-}
-
-hipError_t gemm_launch_pair(const GemmArgs& a, const GemmArgs& b, int epi, hipStream_t stream) {
-  GemmArgs p = a, q = b;
-  p.raster = q.raster = g_gemm_raster ? g_gemm_raster : (p.N >= 8 * BN2 ? 8 : 0);
-  p.dbg_tile0 = q.dbg_tile0 = g_gemm_dbg;
-  if (gemm_pair_groups(p, q, epi)) return launch8s(p, epi, stream, &q);
-  GemmArgs a1 = a, b1 = b;   // one flag block serves one launch
-  a1.sk_flags = b1.sk_flags = nullptr;
-  a1.sk_slab = b1.sk_slab = nullptr;
-  const hipError_t e = gemm_launch(a1, epi, stream);
-  return e != hipSuccess ? e : gemm_launch(b1, epi, stream);
-}
-
-// GemmArgs::gn_part: only the gemm8d (algo 7) and gemm8t (algo 9) epilogues write GroupNorm partials, on whole
-// 256-row tiles of whole images; mirrors gemm_launch's automatic choice for conv / fp32 launches
-bool gemm_gn_fusable(const GemmArgs& p, int epi) {
-  if (g_gemm_algo != 0 || (epi != EPI_F32 && epi != EPI_BF16) || !(p.conv || epi == EPI_F32)) return false;
-  if (p.fp8 || p.out_fp8 || p.batch > 1 || p.a_rows_per_group > 0 || p.ln_stats || p.stats_out || p.A2) return false;
-  if (p.gn_P <= 0 || p.gn_P % 256 || p.M % p.gn_P || p.N % 32 || p.gn_cpg * 32 != p.N) return false;
-  if (p.gn_cpg != 4 && p.gn_cpg != 8 && p.gn_cpg != 16 && p.gn_cpg != 32) return false;
-  const bool a7 = p.M >= 4096 && p.N >= 256, a9 = p.M >= 65536 && p.N > 96 && p.N <= 128;
-  if (!a7 && !a9) return false;
-  if (epi == EPI_BF16 && (p.N % 8 || p.ldo % 8 || ((uintptr_t)p.out_bf16 & 15) || !p.out_bf16)) return false;
-  if (epi == EPI_F32 && (p.N % 8 || p.ldr % 4 || ((uintptr_t)p.out_f32 & 15) ||
-                         (p.out_bf16 && (p.ldo % 8 || ((uintptr_t)p.out_bf16 & 15)))))
+// ... and of their bf16 output (16-byte row chunks), residual input and LayerNorm partials
+static bool fits_persist_out(const GemmArgs& p, int epi) {
+  const long long lim = 0x7fffffffLL;
+  if (!p.out_bf16 || p.N % 8 || p.ldo % 8 || ((uintptr_t)p.out_bf16 & 15) || (long long)p.M * p.ldo * 2 >= lim) return false;
+  if (epi == EPI_RES && p.accumulate && (p.ldri % 8 || ((uintptr_t)p.res_in & 15) || (long long)p.M * p.ldri * 2 >= lim))
     return false;
-  return fits_rsrc(p) || p.conv;   // conv: gemm_launch splits past 2 GiB by whole images
+  return !(p.stats_out && (long long)p.M * p.stats_ld * 8 >= lim);
 }
 
-hipError_t gemm_launch(const GemmArgs& args, int epi, hipStream_t stream) {
-  if (args.gn_part && !gemm_gn_fusable(args, epi)) return hipErrorInvalidValue;
-  GemmArgs p = args;
+// the persistent kernel's preconditions (epilogues, no MXFP8 operands, K >= 256, one A stride); an MXFP8 output only
+// as the sole output of a bf16 / GELU epilogue (gemm_check has validated its shape: N % 32, ldo8 % 16,
+// out_scale_ld >= M)
+static bool fits_8s(const GemmArgs& p, int epi, const GemmPolicy& pol) {
+  const long long lim = 0x7fffffffLL;
+  if (epi != EPI_BF16 && epi != EPI_GELU && epi != EPI_RES) return false;
+  if (p.fp8 || (epi == EPI_GELU && p.act) || p.K < 256 || (p.A2 && p.K1 < p.K && p.lda2 != p.lda1)) return false;
+  if (p.out_fp8) {
+    if (epi == EPI_RES || p.out_bf16 || !p.out_scale || p.N % 32 || p.ldo8 % 16 || p.out_scale_ld < p.M) return false;
+    if ((long long)p.M * p.ldo8 >= lim || (long long)((p.N + 127) >> 7) * p.out_scale_ld * 4 >= lim) return false;
+  } else if (!fits_persist_out(p, epi)) {
+    return false;
+  }
+  return fits_persist(p, pol);
+}
+
+// the persistent kernel's MXFP8-operand form (gemm8s_kernel<EPI, 0, 0, 1>): the bf16 epilogue with or without the
+// (centred) LayerNorm consumer -- the U-ViT-H/4 qkv, algo 11 only -- and the bf16-residual epilogue without an MXFP8
+// output copy -- the H/4 proj in 'fp8' mode (its x feeds the bf16 fc1), automatic where mx_res_persist allows
+static bool fits_8s_mx(const GemmArgs& p, int epi, const GemmPolicy& pol) {
+  if ((epi != EPI_BF16 && epi != EPI_RES) || !p.fp8 || p.out_fp8 || p.A2 || p.K1 != p.K || p.K % 128 || p.K < 512) return false;
+  return fits_persist_out(p, epi) && fits_persist(p, pol);
+}
+
+// the two parts of a launch whose operands pass the descriptor kernels' 2 GiB range: rows [0, m1) and the rest
+static void split_rows(const GemmArgs& p, int m1, GemmArgs& a, GemmArgs& b) {
+  a = b = p;
+  a.sk_flags = b.sk_flags = nullptr;   // one flag block serves one launch
+  a.sk_slab = b.sk_slab = nullptr;
+  a.out2 = b.out2 = nullptr;           // the second output: one copy after both parts
+  a.stats_out2 = b.stats_out2 = nullptr;
+  a.M = m1;
+  b.M = p.M - m1;
+  if (p.conv) b.A1 += (size_t)(m1 / (p.convH * p.convW)) * (p.convH >> p.conv_up) * (p.convW >> p.conv_up) * p.convC;
+  else {
+    b.A1 += (size_t)m1 * p.lda1;
+    if (b.A2) b.A2 += (size_t)m1 * p.lda2;
+  }
+  if (b.out_bf16) b.out_bf16 += (size_t)m1 * p.ldo;
+  if (b.out_f32) b.out_f32 += (size_t)m1 * p.ldr;
+  if (b.res_in) b.res_in += (size_t)m1 * p.ldri;
+  if (b.res_f32) b.res_f32 += (size_t)m1 * p.ldrf;
+  if (b.stats_out) b.stats_out += (size_t)m1 * p.stats_ld * 2;
+  if (b.ln_stats) b.ln_stats += (size_t)m1 * p.ln_ld * 2;
+  if (b.gn_part && p.gn_P > 0) b.gn_part += (size_t)(m1 / p.gn_P) * (p.gn_P >> 8) * 64;   // whole images (conv split)
+}
+
+namespace {
+// a plan of `family` with the given template coordinates: its table row, LDS size and the grid of bm x bn tiles
+GemmPlan plan_tiles(const GemmArgs& p, int family, int bm, int bn, int block, int epi, int conv, int sched, int mxo = 0,
+                    int sk = 0, int fp8 = 0, int dual = 0) {
+  GemmPlan pl{};
+  pl.family = family;
+  pl.epi = epi; pl.conv = conv; pl.sched = sched; pl.mxo = mxo; pl.sk = sk; pl.fp8 = fp8; pl.dual = dual;
+  pl.kernel = -1;
+  for (int i = g_family_rows.begin[family]; i < g_family_rows.begin[family + 1]; ++i) {
+    const KernelRow& k = g_kernels[i];
+    if (k.epi == epi && k.conv == conv && k.sched == sched && k.mxo == mxo && k.sk == sk &&
+        k.fp8 == fp8 && k.dual == dual) {
+      pl.kernel = i;
+      pl.lds_bytes = k.lds;
+      break;
+    }
+  }
+  if (pl.kernel < 0) pl.error = PDM_GEMM_ERR_EPI;
+  pl.tiles_n = (p.N + bn - 1) / bn;
+  pl.ntiles = pl.nt0 = (p.M + bm - 1) / bm * pl.tiles_n;
+  pl.grid_x = pl.ntiles;
+  pl.grid_y = p.batch > 1 ? p.batch : 1;
+  pl.block = block;
+  return pl;
+}
+GemmPlan plan_error(int error) {
+  GemmPlan pl{};
+  pl.error = error;
+  pl.family = pl.kernel = -1;
+  return pl;
+}
+
+// the persistent launches: one workgroup per CU at most; p2: the grouped launch's second problem
+GemmPlan plan_persistent(const GemmArgs& p, int epi, const GemmPolicy& pol, const GemmArgs* p2, bool mx) {
+  if (mx) {
+    GemmPlan pl = plan_tiles(p, PDM_GEMM_8S_MX, BM2, BN2, 512, epi, 0, 0, 0, 0, 1, 0);
+    pl.grid_x = pl.ntiles < pol.ncu ? pl.ntiles : pol.ncu;
+    return pl;
+  }
+  const int tn = (p.N + BN2 - 1) / BN2;
+  const int nt0 = (p.M + BM2 - 1) / BM2 * tn;
+  const int ntiles = nt0 + (p2 ? (p2->M + BM2 - 1) / BM2 * tn : 0);
+  const int grid = ntiles < pol.ncu ? ntiles : pol.ncu;
+  // stream-K where the last wave of tiles leaves CUs idle and every workgroup's share is >= nk + 4 K-steps (so each
+  // tile has at most two pieces and the consumer's tail normally finds its flag up, gemm8s_body)
+  bool sk = false;
+  if (!p2 && p.sk_flags && p.sk_slab && pol.sk && ntiles > grid && grid <= SK_FLAG_WORDS && grid >= 8 && ntiles % grid) {
+    const int nk = p.K / 64, gx = (grid + 7) / 8, tmin = ntiles / 8;
+    const int waves = (ntiles + grid - 1) / grid;
+    const double fill = (double)ntiles / ((double)waves * grid);
+    sk = (long long)tmin * nk >= (long long)gx * (nk + 4) && (pol.sk == 2 || fill < 0.97);
+  }
+  const int dual = p.A2 && p.K1 < p.K;
+  const int mxo = p.out_fp8 ? 1 : 0;
+  // both problems of a grouped launch share A2's presence and K1 (gemm_plan_pair)
+  GemmPlan pl = sk                ? plan_tiles(p, PDM_GEMM_8S, BM2, BN2, 512, epi, 0, 0, mxo, 1, 0, 1)
+                : (p2 && !mxo)    ? plan_tiles(p, PDM_GEMM_8G, BM2, BN2, 512, epi, 0, 0, 0, 0, 0, dual)
+                                  : plan_tiles(p, PDM_GEMM_8S, BM2, BN2, 512, epi, 0, 0, mxo, 0, 0, dual);
+  pl.ntiles = ntiles;
+  pl.nt0 = p2 ? nt0 : ntiles;
+  pl.grid_x = grid;
+  return pl;
+}
+}  // namespace
+
+// The kernel choice.  algo: 0 auto, 1 = 128x128, 2 = 256x256 BK32 x4 ring, 3 = 256x256 BK64 x2, 4 = 8-phase, 5 / 6 / 7 =
+// descriptor-addressed 8-phase (schedules 0 / 1 / 2), 8 = half-N tile, 9 = tall tile, 11 = persistent
+GemmPlan gemm_plan(const GemmArgs& p, int epi, const GemmPolicy& pol) {
   // tile order: groups of 8 row panels once there are >= 8 column tiles (an XCD's 32 resident tiles then share
   // 4 A and 8 W panels instead of 2 and 16); measured by tools/gemm_tune.py
-  p.raster = g_gemm_raster ? g_gemm_raster : (p.N >= 8 * BN2 ? 8 : 0);
-  p.dbg_tile0 = g_gemm_dbg;
-  int algo = g_gemm_algo;
+  const int raster = pol.raster ? pol.raster : (p.N >= 8 * BN2 ? 8 : 0);
+  // GemmArgs::gn_part: only the gemm8d and gemm8t epilogues write GroupNorm partials, on whole 256-row tiles, and
+  // the launcher vouches for them under the automatic policy, on the fp32 epilogue or a conv's bf16 one, of a plain
+  // launch (no MXFP8, batch, gather, LayerNorm fusion or split-K operand)
+  const bool gn_epilogue = pol.algo == 0 && (epi == EPI_F32 || (epi == EPI_BF16 && p.conv)) && !p.fp8 && !p.out_fp8 &&
+                           p.batch <= 1 && p.a_rows_per_group <= 0 && !p.ln_stats && !p.stats_out && !p.A2;
+  auto done = [&](GemmPlan pl) {
+    pl.raster = raster;
+    pl.writes_gn = gn_epilogue && !pl.error && (pl.family == PDM_GEMM_8D || pl.family == PDM_GEMM_8T);
+    return pl;
+  };
+  int algo = pol.algo;
   const long long rows_all = (long long)p.M * (p.batch > 1 ? p.batch : 1);
   // batched GEMMs (decoder AttnBlock q k^T and p v, 1024 rows per image at 256^2) count all batches' rows
   // 96 < N <= 128 with many rows (the decoder's 128-channel 512^2 convs and nin_shortcut): the 512 x 128 tall
@@ -3416,10 +3258,10 @@ hipError_t gemm_launch(const GemmArgs& args, int epi, hipStream_t stream) {
   // tile, algo 8, measured 1070 us and is kept as an option only: tools/conv_bench.py, profiles/r03q)
   if (algo == 0) {
     algo = (rows_all >= 4096 && p.N >= 256) ? 7 : (rows_all >= 65536 && p.N > 96 && p.N <= 128 && p.batch <= 1) ? 9 : 1;
-    if (algo == 7 && fits_8s(p, epi)) algo = 11;   // the persistent kernel where its epilogues apply
+    if (algo == 7 && fits_8s(p, epi, pol)) algo = 11;   // the persistent kernel where its epilogues apply
   }
   if (algo == 11) {
-    if (!p.fp8 && fits_8s(p, epi)) return launch8s(p, epi, stream);
+    if (!p.fp8 && fits_8s(p, epi, pol)) return done(plan_persistent(p, epi, pol, nullptr, false));
     algo = 7;
   }
   if ((algo == 8 || algo == 9) && (p.N > 128 || (epi != EPI_BF16 && epi != EPI_F32) || p.ln_stats || p.stats_out ||
@@ -3429,19 +3271,21 @@ hipError_t gemm_launch(const GemmArgs& args, int epi, hipStream_t stream) {
   if (epi == EPI_F32 && (p.N % 8 || p.ldr % 4 || ((uintptr_t)p.out_f32 & 15) ||
                          (p.out_bf16 && (p.ldo % 8 || ((uintptr_t)p.out_bf16 & 15))))) algo = 1;
   if (p.fp8) {
-    if (!fits_rsrc(p)) return hipErrorInvalidValue;
+    if (!fits_rsrc(p)) return plan_error(PDM_GEMM_ERR_FP8_RANGE);
     // the persistent form under the automatic policy from 16 sequences of 258 tokens up (round 6, after its
     // issue-path changes): the H/4 forward at the bench's 50-row lanes 13.12 -> 12.99 ms with it on every MXFP8
     // shape (qkv with the centred LayerNorm consumer, proj, fc2; tools/forward_algo_ab.py, profiles/r06al); the
     // residual form alone: 64.3 -> 57.2 us at 100 rows, parity at 25-50 (tools/mx_res_bench.py, profiles/r06v)
-    if ((g_gemm_algo == 11 || (g_gemm_algo == 0 && g_mx_res_persist && p.M >= 4096)) && fits_8s_mx(p, epi))
-      return launch8s_mx(p, epi, stream);
-    return launch_mx(p, epi, stream);
+    if ((pol.algo == 11 || (pol.algo == 0 && pol.mx_res_persist && p.M >= 4096)) && fits_8s_mx(p, epi, pol))
+      return done(plan_persistent(p, epi, pol, nullptr, true));
+    GemmPlan pl = plan_tiles(p, PDM_GEMM_MX, BM2, BN2, 512, epi, 0, 0, 0, 0, 1, 0);
+    pl.grid_y = 1;
+    return done(pl);
   }
   if (p.out_fp8) algo = 7;   // MXFP8 output lives in the 256-tile epilogue
   // no-store timing mode (pdm_set_gemm_tuning bit 1, gemm_check): only the 256-tile epilogue skips a missing output
   if ((epi == EPI_BF16 || epi == EPI_GELU) && !p.out_bf16 && !p.out_fp8) {
-    if (!fits_rsrc(p) || p.conv || p.batch > 1) return hipErrorInvalidValue;
+    if (!fits_rsrc(p) || p.conv || p.batch > 1) return plan_error(PDM_GEMM_ERR_NOSTORE);
     algo = 7;
   }
   // operands past the descriptor kernels' 2 GiB byte-offset range (e.g. a 32-image chunk of 512^2 x 256-channel
@@ -3451,64 +3295,140 @@ hipError_t gemm_launch(const GemmArgs& args, int epi, hipStream_t stream) {
     const int hw = p.conv ? p.convH * p.convW : 1;
     const int m1 = p.conv ? (p.M / hw / 2) * hw : ((p.M / 2 + BM2 - 1) / BM2) * BM2;
     if (m1 > 0 && m1 < p.M) {
-      GemmArgs a = args, b = args;
-      a.sk_flags = b.sk_flags = nullptr;   // one flag block serves one launch
-      a.sk_slab = b.sk_slab = nullptr;
-      a.out2 = b.out2 = nullptr;           // the second output: one copy after both parts
-      a.stats_out2 = b.stats_out2 = nullptr;
-      a.M = m1;
-      b.M = p.M - m1;
-      if (p.conv) b.A1 += (size_t)(m1 / hw) * (p.convH >> p.conv_up) * (p.convW >> p.conv_up) * p.convC;
-      else {
-        b.A1 += (size_t)m1 * p.lda1;
-        if (b.A2) b.A2 += (size_t)m1 * p.lda2;
-      }
-      if (b.out_bf16) b.out_bf16 += (size_t)m1 * p.ldo;
-      if (b.out_f32) b.out_f32 += (size_t)m1 * p.ldr;
-      if (b.res_in) b.res_in += (size_t)m1 * p.ldri;
-      if (b.res_f32) b.res_f32 += (size_t)m1 * p.ldrf;
-      if (b.stats_out) b.stats_out += (size_t)m1 * p.stats_ld * 2;
-      if (b.ln_stats) b.ln_stats += (size_t)m1 * p.ln_ld * 2;
-      if (b.gn_part) b.gn_part += (size_t)(m1 / p.gn_P) * (p.gn_P >> 8) * 64;   // whole images (conv split)
-      hipError_t e = gemm_launch(a, epi, stream);
-      if (e == hipSuccess) e = gemm_launch(b, epi, stream);
-      if (e == hipSuccess && p.out2) e = out2_copy(p, stream);
-      return e;
+      GemmArgs a, b;
+      split_rows(p, m1, a, b);
+      const GemmPlan pa = gemm_plan(a, epi, pol), pb = gemm_plan(b, epi, pol);
+      GemmPlan pl = pa;
+      pl.split_m1 = m1;
+      if (!pl.error) pl.error = pb.error;
+      pl.rowstats = 0;   // the parts run their own
+      pl.out2_copy = p.out2 != nullptr;
+      // the parts of a conv are whole images; a Linear's are not, so its partials cannot come from the epilogue
+      pl.writes_gn = p.conv && pa.writes_gn && pb.writes_gn;
+      return pl;
     }
   }
-  if (algo == 8 && fits_rsrc(p)) return p.conv ? launch8d_hn<1>(p, epi, stream) : launch8d_hn<0>(p, epi, stream);
-  if (algo == 9 && fits_rsrc(p)) return p.conv ? launch8t<1>(p, epi, stream) : launch8t<0>(p, epi, stream);
+  if ((algo == 8 || algo == 9) && fits_rsrc(p)) {
+    if (p.N > 128 || (algo == 9 && p.batch > 1) || (epi != EPI_BF16 && epi != EPI_F32)) return plan_error(PDM_GEMM_ERR_GUARD);
+    if (algo == 8) return done(plan_tiles(p, PDM_GEMM_8D_HN, BM2, 128, 512, epi, p.conv ? 1 : 0, 2));
+    return done(plan_tiles(p, PDM_GEMM_8T, 512, 128, 512, epi, p.conv ? 1 : 0, 0));
+  }
   if (algo == 8 || algo == 9) algo = 1;
   if (epi == EPI_RES) {      // the residual epilogue exists in the default 256-tile schedule and the 128 tile
-    if (algo != 1 && fits_rsrc(p)) return launch8d<0, 2>(p, epi, stream);
+    if (algo != 1 && fits_rsrc(p)) return done(plan_tiles(p, PDM_GEMM_8D, BM2, BN2, 512, EPI_RES, 0, 2));
     algo = 1;
   }
-  if (algo >= 5 && fits_rsrc(p)) {
-    if (algo == 5) return p.conv ? launch8d<1, 0>(p, epi, stream) : launch8d<0, 0>(p, epi, stream);
-    if (algo == 6) return p.conv ? launch8d<1, 1>(p, epi, stream) : launch8d<0, 1>(p, epi, stream);
-    return p.conv ? launch8d<1, 2>(p, epi, stream) : launch8d<0, 2>(p, epi, stream);
-  }
+  if (algo >= 5 && fits_rsrc(p))
+    return done(plan_tiles(p, PDM_GEMM_8D, BM2, BN2, 512, epi, p.conv ? 1 : 0, algo == 5 ? 0 : algo == 6 ? 1 : 2));
   if (algo >= 5) algo = 3;
-  if (algo == 2 && p.K % 32 == 0) return launch256<32, 4>(p, epi, stream);
-  if (algo == 4 && p.K % 128 == 0) return p.conv ? launch8p<1>(p, epi, stream) : launch8p<0>(p, epi, stream);
-  if ((algo == 3 || algo == 4) && p.K % 64 == 0) return launch256<64, 2>(p, epi, stream);
-  const int tiles_n = (p.N + BN - 1) / BN;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  const int nwg = tiles_m * tiles_n;
-  dim3 grid(nwg, p.batch > 1 ? p.batch : 1), block(256);
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL(gemm_bf16_kernel<EPI_BF16>, grid, block, SMEM_BYTES, stream, p, tiles_n, nwg); break;
-    case EPI_GELU: hipLaunchKernelGGL(gemm_bf16_kernel<EPI_GELU>, grid, block, SMEM_BYTES, stream, p, tiles_n, nwg); break;
-    case EPI_RES: hipLaunchKernelGGL(gemm_bf16_kernel<EPI_RES>, grid, block, SMEM_BYTES, stream, p, tiles_n, nwg); break;
-    default: hipLaunchKernelGGL(gemm_bf16_kernel<EPI_F32>, grid, block, SMEM_BYTES, stream, p, tiles_n, nwg); break;
-  }
-  hipError_t e = hipGetLastError();
+  if (algo == 2 && p.K % 32 == 0) return done(plan_tiles(p, PDM_GEMM_RING32, BM2, BN2, 512, epi, 0, 0));
+  if (algo == 4 && p.K % 128 == 0) return done(plan_tiles(p, PDM_GEMM_8P, BM2, BN2, 512, epi, p.conv ? 1 : 0, 0));
+  if ((algo == 3 || algo == 4) && p.K % 64 == 0) return done(plan_tiles(p, PDM_GEMM_RING64, BM2, BN2, 512, epi, 0, 0));
+  GemmPlan pl = plan_tiles(p, PDM_GEMM_128, BM, BN, 256, epi, 0, 0);
   // the 128-tile epilogue spreads a row over two waves: its LayerNorm partials come from a row pass instead
-  if (e == hipSuccess && p.stats_out && p.batch <= 1) {
-    if (epi == EPI_RES) e = rowstats_bf16_launch(p.out_bf16, p.ldo, p.M, p.N, p.stats_out, p.stats_ld, stream);
-    else e = rowstats_launch(p.out_f32, p.ldr, p.M, p.N, nullptr, 0, p.stats_out, p.stats_ld, stream);
+  pl.rowstats = p.stats_out && p.batch <= 1;
+  pl.out2_copy = epi == EPI_RES && p.out2;
+  return done(pl);
+}
+
+// grouped only where each GEMM alone would take the persistent kernel under the automatic policy, so a problem's
+// arithmetic -- and the sampler's batch invariance -- does not depend on the other problem's rows
+bool gemm_plan_pair(const GemmArgs& a, const GemmArgs& b, int epi, const GemmPolicy& pol, GemmPlan* out) {
+  GemmArgs p = a, q = b;
+  p.sk_flags = q.sk_flags = nullptr;
+  const bool same = p.N == q.N && p.K == q.K && p.K1 == q.K1 && p.lda1 == q.lda1 && p.ldw == q.ldw && p.ldo == q.ldo &&
+                    p.ldri == q.ldri && p.accumulate == q.accumulate && p.stats_ld == q.stats_ld && p.ln_ld == q.ln_ld &&
+                    p.ln_D == q.ln_D && p.ln_eps == q.ln_eps && !p.bias == !q.bias && !p.ln_stats == !q.ln_stats &&
+                    !p.stats_out == !q.stats_out && !p.A2 == !q.A2 && (!p.A2 || p.lda2 == q.lda2) && !p.out_fp8 && !q.out_fp8;
+  if (!same || (pol.algo != 0 && pol.algo != 11)) return false;
+  GemmPolicy aut = pol;
+  aut.algo = 0;
+  const GemmPlan pp = gemm_plan(p, epi, aut), pq = gemm_plan(q, epi, aut);
+  if (pp.error || pq.error || pp.family != PDM_GEMM_8S || pq.family != PDM_GEMM_8S) return false;
+  GemmPlan pl = plan_persistent(p, epi, pol, &q, false);
+  pl.raster = pp.raster;
+  if (out) *out = pl;
+  return !pl.error;
+}
+bool gemm_pair_groups(const GemmArgs& p, const GemmArgs& q, int epi) {
+  return gemm_plan_pair(p, q, epi, gemm_policy(), nullptr);
+}
+
+// whether gemm_launch writes p.gn_part: whole 256-row tiles of whole images, 32 groups of 4 / 8 / 16 / 32 columns, and
+// a plan whose epilogue writes them
+static bool gn_shape_ok(const GemmArgs& p) {
+  if (p.gn_P <= 0 || p.gn_P % 256 || p.M % p.gn_P || p.N % 32 || p.gn_cpg * 32 != p.N) return false;
+  return p.gn_cpg == 4 || p.gn_cpg == 8 || p.gn_cpg == 16 || p.gn_cpg == 32;
+}
+bool gemm_gn_fusable(const GemmArgs& p, int epi, const GemmPolicy& pol) {
+  return gn_shape_ok(p) && gemm_plan(p, epi, pol).writes_gn;
+}
+bool gemm_gn_fusable(const GemmArgs& p, int epi) { return gemm_gn_fusable(p, epi, gemm_policy()); }
+
+// the plan's kernel on the stream; the first launch of a family sets the dynamic-LDS limit of all its instantiations
+static hipError_t launch_plan(const GemmPlan& pl, GemmArgs& p, const GemmArgs* p2, hipStream_t stream) {
+  static bool attr_set[PDM_GEMM_FAMILIES] = {};
+  if (!attr_set[pl.family]) {
+    for (int i = g_family_rows.begin[pl.family]; i < g_family_rows.begin[pl.family + 1]; ++i)
+      if (g_kernels[i].lds > 64 * 1024)
+        (void)hipFuncSetAttribute(g_kernels[i].fn, hipFuncAttributeMaxDynamicSharedMemorySize, g_kernels[i].lds);
+    attr_set[pl.family] = true;
   }
-  if (e == hipSuccess && epi == EPI_RES && p.out2) e = out2_copy(p, stream);
+  int tiles_n = pl.tiles_n, ntiles = pl.ntiles, nt0 = pl.nt0;
+  TV second = view_of(p2 ? *p2 : p);
+  void* tile_args[] = {&p, &tiles_n, &ntiles};                    // every family but the two below
+  void* tall_args[] = {&p, &ntiles};                              // gemm8t_kernel
+  void* pair_args[] = {&p, &tiles_n, &ntiles, &second, &nt0};     // gemm8g_kernel
+  return hipLaunchKernel(g_kernels[pl.kernel].fn, dim3(pl.grid_x, pl.grid_y), dim3(pl.block),
+                         pl.family == PDM_GEMM_8T ? tall_args : pl.family == PDM_GEMM_8G ? pair_args : tile_args,
+                         pl.lds_bytes, stream);
+}
+
+// the second residual output of a launch whose kernel has no out2 store (the 128 tile, a split launch): the rows
+// (and partials) copied from out_bf16 / stats_out after it, as 4-byte words
+static hipError_t out2_copy(const GemmArgs& p, hipStream_t stream) {
+  return rowcopy_launch(reinterpret_cast<float*>(p.out2), p.ldo / 2, reinterpret_cast<const float*>(p.out_bf16),
+                        p.ldo / 2, p.M, p.N / 2, p.out2_rpg, p.out2_gs, p.out2_rpg, stream, p.stats_out2,
+                        p.stats_ld * 2, p.stats_out, p.stats_ld * 2, p.stats_out2 ? p.stats_ld * 2 : 0);
+}
+
+hipError_t gemm_launch_pair(const GemmArgs& a, const GemmArgs& b, int epi, hipStream_t stream) {
+  GemmPlan pl;
+  if (gemm_plan_pair(a, b, epi, gemm_policy(), &pl)) {
+    GemmArgs p = a, q = b;
+    p.raster = q.raster = pl.raster;
+    p.dbg_tile0 = q.dbg_tile0 = g_gemm_dbg;
+    return launch_plan(pl, p, &q, stream);
+  }
+  GemmArgs a1 = a, b1 = b;   // one flag block serves one launch
+  a1.sk_flags = b1.sk_flags = nullptr;
+  a1.sk_slab = b1.sk_slab = nullptr;
+  const hipError_t e = gemm_launch(a1, epi, stream);
+  return e != hipSuccess ? e : gemm_launch(b1, epi, stream);
+}
+
+hipError_t gemm_launch(const GemmArgs& args, int epi, hipStream_t stream) {
+  const GemmPolicy pol = gemm_policy();
+  const GemmPlan pl = gemm_plan(args, epi, pol);
+  if (pl.error || (args.gn_part && !(gn_shape_ok(args) && pl.writes_gn))) return hipErrorInvalidValue;
+  hipError_t e;
+  if (pl.split_m1) {
+    GemmArgs a, b;
+    split_rows(args, pl.split_m1, a, b);
+    e = gemm_launch(a, epi, stream);
+    if (e == hipSuccess) e = gemm_launch(b, epi, stream);
+  } else {
+    GemmArgs p = args;
+    p.raster = pl.raster;
+    p.dbg_tile0 = pol.dbg;
+    if (pl.sk) ++g_sk_launches;
+    e = launch_plan(pl, p, nullptr, stream);
+  }
+  if (e == hipSuccess && pl.rowstats) {
+    if (epi == EPI_RES) e = rowstats_bf16_launch(args.out_bf16, args.ldo, args.M, args.N, args.stats_out, args.stats_ld, stream);
+    else e = rowstats_launch(args.out_f32, args.ldr, args.M, args.N, nullptr, 0, args.stats_out, args.stats_ld, stream);
+  }
+  if (e == hipSuccess && pl.out2_copy) e = out2_copy(args, stream);
   return e;
 }
 

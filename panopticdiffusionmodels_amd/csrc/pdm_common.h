@@ -15,6 +15,17 @@ typedef int i32x2 __attribute__((ext_vector_type(2)));
 
 #define PDM_LDS __attribute__((address_space(3)))
 
+// compute units of the current device, asked once (the persistent kernels' grids); 256 if the runtime will not say
+inline int device_ncu() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
+      return n;
+    return 256;
+  }();
+  return ncu;
+}
+
 __device__ __forceinline__ f32x4 mfma16x16x32(const bf16x8& a, const bf16x8& b, const f32x4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }

@@ -125,6 +125,38 @@ bool gemm_pair_groups(const GemmArgs& a, const GemmArgs& b, int epi);
 // and mask-stream Linears of a layer); otherwise the two launches of gemm_launch, in order
 hipError_t gemm_launch_pair(const GemmArgs& a, const GemmArgs& b, int epi, hipStream_t stream);
 void gemm_set_algo(int algo);
+// Every decision of gemm_launch / gemm_launch_pair as a pure function of the arguments and a snapshot of the process
+// state (GemmPolicy): gemm_plan reads no global, calls no HIP function and dereferences no operand pointer (only their
+// null-ness and low address bits count).  gemm_launch, gemm_pair_groups and gemm_gn_fusable all read its result.
+struct GemmPolicy {
+  int algo;             // gemm_set_algo (0: automatic)
+  int sk;               // gemm_set_sk
+  int raster, dbg;      // gemm_set_tuning
+  int mx_res_persist;   // the MXFP8-operand Linears on the persistent kernel under the automatic policy
+  int ncu;              // compute units of the device (the persistent kernels' grids)
+  int persist_ok;       // no persistent instantiation spills (gemm.hip persist_kernels_ok)
+};
+struct GemmPlan {
+  int error;            // PDM_GEMM_ERR_* (include/pdm.h); 0: the launch is possible
+  int family;           // PDM_GEMM_*; of a row split: the first part's
+  // the instantiation's template coordinates (0 where the family's template has none) and its row in gemm.hip's table
+  int epi, conv, sched, mxo, sk, fp8, dual;
+  int kernel;
+  int grid_x, grid_y, block, lds_bytes;
+  int tiles_n, ntiles;  // the kernel's tile arguments (ntiles: workgroups of the whole-tile kernels)
+  int nt0;              // grouped launch: the first problem's tiles (else ntiles)
+  int raster;           // GemmArgs::raster of the launch
+  int split_m1;         // > 0: rows [0, split_m1) and the rest are two launches, each planned by gemm_plan again
+  int rowstats;         // post-pass: LayerNorm partials by a row pass (the 128 tile)
+  int out2_copy;        // post-pass: the second residual output copied from the first (the 128 tile, a row split)
+  int writes_gn;        // the epilogue writes GemmArgs::gn_part (if set), on every part of a split
+};
+GemmPolicy gemm_policy(int ncu = -1, int persist_ok = -1);   // this process's state; < 0: asks the device (once)
+GemmPlan gemm_plan(const GemmArgs& p, int epi, const GemmPolicy& pol);
+// the grouped launch of gemm_launch_pair (family PDM_GEMM_8G) into *pl, or false: two launches of gemm_plan's choice
+bool gemm_plan_pair(const GemmArgs& a, const GemmArgs& b, int epi, const GemmPolicy& pol, GemmPlan* pl);
+// the GroupNorm-partials rule of gemm_gn_fusable under a given policy
+bool gemm_gn_fusable(const GemmArgs& p, int epi, const GemmPolicy& pol);
 
 // LayerNorm over the last dim of fp32 rows -> bf16.  Row r of the output is row
 // (r / rows_per_group) * group_stride + row_offset + (r % rows_per_group) of the input.

@@ -23,6 +23,15 @@ def lib():
     return _lib
 
 
+def family(lib, epi, *shape, second=None, conv=None, batch=0, **opts):
+    """The kernel family pdm_gemm_plan names for this launch under the process's current policy (asked while a test's
+    forced algo is set): error-free, printed once per case.  shape / opts: _lib.gemm_shape_args."""
+    pl = lib.gemm_plan(lib.gemm_shape_args(*shape, epi, **opts), epi, second=second, conv=conv, batch=batch)
+    assert pl.error is None, pl
+    print(f"gemm plan {shape} epi {epi}: {pl.family}" + (f", rows split at {pl.split_m1}" if pl.split_m1 else ""))
+    return pl.family
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (300, 256, 512), (25800 // 8, 1024, 1024), (77, 64, 64),
                                    (1000, 192, 256), (4096, 3456, 1152), (129, 4608, 1152)])
 @pytest.mark.parametrize("epi", ["bf16", "gelu", "f32", "f32acc"])
@@ -100,10 +109,17 @@ def test_gemm_algos(lib, algo, M, N, K, epi):
     ref = a.float() @ w.float().t() + bias
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        # the docstring's kernels (every N here is a multiple of 8, so no alignment fallback); the persistent kernel
+        # (11) has no fp32 epilogue and needs K >= 256: algo 7's kernel otherwise
+        want = {1: "128", 2: "ring32", 3: "ring64", 4: "8p" if K % 128 == 0 else "ring64", 5: "8d", 6: "8d", 7: "8d",
+                8: "8d_hn" if N <= 128 and epi != "gelu" else "128", 9: "8t" if N <= 128 and epi != "gelu" else "128",
+                11: "8s" if epi == "gelu" and K >= 256 else "8d"}[algo]   # 8 / 9: bf16 / fp32 epilogues only
         if epi == "gelu":
+            assert family(lib, lib.EPI_GELU, M, N, K) == want
             out = lib.gemm(a, w, bias, lib.EPI_GELU)
             assert rel(out.float(), F.gelu(ref)) < 1e-2
         elif epi == "f32acc_copy":
+            assert family(lib, lib.EPI_F32, M, N, K, copy=True, accumulate=True) == want
             r0 = torch.randn(M, N, device="cuda", generator=g)
             cp = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
             out = lib.gemm(a, w, bias, lib.EPI_F32, out=cp, out_f32=r0.clone(), accumulate=True)
@@ -112,6 +128,7 @@ def test_gemm_algos(lib, algo, M, N, K, epi):
         else:
             h = (K // 128) * 64 if K >= 128 else K   # split point on a 64-column boundary; K = 64 runs unsplit
             a2 = a[:, h:].contiguous() if h < K else None
+            assert family(lib, lib.EPI_F32, M, N, K, K1=h) == want
             out = lib.gemm(a[:, :h].contiguous(), w, bias, lib.EPI_F32, a2=a2)
             assert rel(out, ref) < 2e-3
     finally:
@@ -137,6 +154,13 @@ def test_gemm_conv3x3(lib, algo, B, h, Cin, N, up, epi):
     ref = F.conv2d(xin, w.float(), bias, padding=1).permute(0, 2, 3, 1).reshape(-1, N)
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        H = h << up
+        fam = family(lib, lib.EPI_BF16 if epi == "bf16" else lib.EPI_F32, B * H * H, N, 9 * Cin, conv=(H, H, Cin, up),
+                     conv_C=Cin, accumulate=epi == "f32acc")
+        # N % 8 != 0 (the 4-channel conv) takes the 128 tile under every algo; 8 / 9 need N <= 128
+        assert fam == ("128" if N % 8 else {1: "128", 3: "ring64", 4: "8p" if Cin % 128 == 0 else "ring64", 5: "8d", 6: "8d",
+                                            7: "8d", 8: "8d_hn" if N <= 128 else "128",
+                                            9: "8t" if N <= 128 else "128"}[algo])   # 8p: K = 9 Cin a multiple of 128
         if epi == "bf16":
             out = lib.gemm_conv3x3(x, w, bias, lib.EPI_BF16, up=up)
             assert rel(out.float(), ref) < 1e-2
@@ -197,6 +221,9 @@ def test_gemm_batched(lib, algo, Z, M, N, K):
     ref = torch.bmm(a.float(), w.float().transpose(1, 2))
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        for e in (lib.EPI_F32, lib.EPI_BF16):   # N = 260 is no multiple of 8: the 128 tile
+            assert family(lib, e, M, N, K, batch=Z) == ("128" if N % 8 else {1: "128", 3: "ring64", 4: "8p" if K % 128 == 0
+                                                                            else "ring64", 5: "8d", 6: "8d", 7: "8d"}[algo])
         out = lib.gemm_batched(a, w, None, lib.EPI_F32)
         assert rel(out, ref) < 2e-3
         outb = lib.gemm_batched(a, w, None, lib.EPI_BF16)
@@ -247,6 +274,8 @@ def test_gemm_layernorm_consumer(lib, algo, M, N, K, epi):
     xb, st = lib.rowstats(x)
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        fam = family(lib, lib.EPI_GELU if epi == "gelu" else lib.EPI_BF16, M, N, K, ln=True)
+        assert fam == {1: "128", 3: "ring64", 4: "8p", 5: "8d", 6: "8d", 7: "8d", 11: "8s"}[algo]
         out = lib.gemm_ln(xb, wg, bias, lib.EPI_GELU if epi == "gelu" else lib.EPI_BF16, ln_stats=st, ln_colsum=colsum)
     finally:
         lib.load().pdm_set_gemm_algo(0)
@@ -265,6 +294,8 @@ def test_gemm_layernorm_producer(lib, algo, M, N, K):
     cp = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        fam = family(lib, lib.EPI_F32, M, N, K, copy=True, accumulate=True, stats=True)
+        assert fam == {1: "128", 3: "ring64", 4: "8p", 5: "8d", 6: "8d", 7: "8d"}[algo]
         out, st = lib.gemm_ln(a, w, bias, lib.EPI_F32, out=cp, out_f32=r0.clone(), accumulate=True, stats_out=True)
     finally:
         lib.load().pdm_set_gemm_algo(0)
@@ -290,6 +321,9 @@ def test_gemm_residual_bf16(lib, algo, M, N, K, mode):
     st = torch.empty(M, (N + 255) // 256, 2, device="cuda")
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        # the residual epilogue: persistent from K >= 256 (automatic: from 4096 rows of N >= 256), algo 7's kernel, the 128 tile
+        fam = family(lib, lib.EPI_RES, M, N, K, accumulate=mode != "noacc", stats=True)
+        assert fam == {0: "8s" if M >= 4096 else "128", 1: "128", 7: "8d", 11: "8s" if K >= 256 else "8d"}[algo]
         lib.gemm_ex(lib.EPI_RES, a, w, bias, out=out, res_in=None if mode == "noacc" else (out if mode == "inplace" else res),
                     accumulate=mode != "noacc", stats_out=st)
     finally:
@@ -313,6 +347,8 @@ def test_gemm_residual_f32_out_of_place(lib, algo, M, N, K):
     cp = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
     lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
     try:
+        fam = family(lib, lib.EPI_F32, M, N, K, copy=True, accumulate=True)   # res_f32 changes no decision
+        assert fam == {0: "8d" if M >= 4096 else "128", 1: "128", 3: "ring64", 7: "8d"}[algo]
         lib.gemm_ex(lib.EPI_F32, a, w, bias, out=cp, out_f32=out, accumulate=True, res_f32=res)
     finally:
         lib.load().pdm_set_gemm_algo(0)
@@ -343,6 +379,10 @@ def test_gemm_persistent(lib, M, N, K, kind):
     for algo in (7, 11):
         lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
         try:
+            e = {"ln": lib.EPI_BF16, "ln_gelu": lib.EPI_GELU, "bf16": lib.EPI_BF16}.get(kind, lib.EPI_RES)
+            fam = family(lib, e, M, N, K, K1=Ka, ln=kind in ("ln", "ln_gelu"), stats=e == lib.EPI_RES,
+                         accumulate=e == lib.EPI_RES)
+            assert fam == {7: "8d", 11: "8s"}[algo]   # the persistent kernel against the per-tile one, as the docstring says
             if kind in ("ln", "ln_gelu"):
                 x = torch.randn(M, K, device="cuda", generator=torch.Generator(device="cuda").manual_seed(9)) * 1.5 + 2.0
                 xb, st = lib.rowstats(x)
@@ -604,8 +644,14 @@ def test_gemm_pair_grouped_vs_separate(lib, case):
     init = [kw["out"].clone() for kw in (pa, pb)]
     ref = []
     for kw in (pa, pb):
+        alone = lib.gemm_plan(lib._gemm_args(**kw), epi)
+        assert alone.error is None and alone.family == "8s", alone   # each alone: the persistent kernel
         lib.gemm_ex(epi, **kw)
         ref.append({k: kw[k].clone() for k in ("out", "stats_out") if k in kw})
+    pl = lib.gemm_plan(lib._gemm_args(**pa), epi, second=lib._gemm_args(**pb))
+    print(f"gemm plan pair {case}: {pl.family}, grouped {pl.grouped}")
+    assert pl.error is None and (pl.family, pl.grouped) == (("8s", False) if case == "mixed_n" else ("8g", True)), pl
+    assert pl.dual == (case == "skip_split")
     for kw, o in zip((pa, pb), init):
         if case == "fc2_res_inplace":
             kw["out"].copy_(o)     # the residual it reads
@@ -656,6 +702,12 @@ def test_gemm_gather_second_output(lib, G, Lx, Lm, algo):
         lib.check(lib.load().pdm_set_gemm_algo(algo or (7 if M >= 4096 else 1)), "pdm_set_gemm_algo")
         lib.gemm_ex(lib.EPI_RES, a_c, w, bias, out=out_ref, res_in=res, accumulate=True, stats_out=st_ref)
         lib.check(lib.load().pdm_set_gemm_algo(algo), "pdm_set_gemm_algo")
+        pl = lib.gemm_plan(lib._gemm_args(src, w, bias, out=out, res_in=res, accumulate=True, stats_out=st,
+                                          a_gather=(M, Lx, Lm), out2=mb, out2_gather=(Lx, Lm), stats_out2=stm), lib.EPI_RES)
+        print(f"gemm plan gathered {M} rows, algo {algo}: {pl.family}, out2 copy {pl.out2_copy}")
+        big = algo == 0 and M >= 4096   # the docstring's kernels: the 256 tile stores out2 itself, the 128 tile's is copied
+        assert pl.error is None and (pl.family, pl.out2_copy, pl.rowstats) == (("8d", False, False) if big else
+                                                                              ("128", True, True)), pl
         lib.gemm_ex(lib.EPI_RES, src, w, bias, out=out, res_in=res, accumulate=True, stats_out=st,
                     a_gather=(M, Lx, Lm), out2=mb, out2_gather=(Lx, Lm), stats_out2=stm)
         torch.cuda.synchronize()

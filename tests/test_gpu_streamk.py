@@ -76,6 +76,9 @@ def _outputs(kw):
     return {k: kw[k] for k in ("out", "stats_out", "out_fp8", "out_scale") if k in kw}
 
 
+SK_PLANNED = [0]   # launches whose plan (pdm_gemm_plan under the policy _run sets) says SK = 1
+
+
 def _run(lib, epi, kw, init, mode, dbg=0):
     """One launch from the same initial output state; returns copies of every output."""
     for k, v in init.items():
@@ -84,6 +87,9 @@ def _run(lib, epi, kw, init, mode, dbg=0):
     lib.check(L.pdm_set_gemm_sk(mode), "pdm_set_gemm_sk")
     L.pdm_set_gemm_tuning(0, dbg)
     try:
+        pl = lib.gemm_plan(lib._gemm_args(**kw), epi, sk_attached=bool(mode & 4))
+        assert pl.error is None and pl.family == "8s", pl
+        SK_PLANNED[0] += pl.sk
         lib.gemm_ex(epi, **kw)
         torch.cuda.synchronize()
     finally:
@@ -98,9 +104,10 @@ def test_streamk_bit_identical(lib, name, M, N, K, kind):
     init = {k: v.clone() for k, v in _outputs(kw).items()}
     L = lib.load()
     whole = _run(lib, epi, kw, init, 0)
-    n0 = L.pdm_gemm_sk_launches()
+    n0, p0 = L.pdm_gemm_sk_launches(), SK_PLANNED[0]
     sk = _run(lib, epi, kw, init, 2 | 4)
     assert L.pdm_gemm_sk_launches() == n0 + 1, "stream-K was not taken for this shape"
+    assert SK_PLANNED[0] == p0 + 1, "the plan does not say stream-K for this shape"
     sk2 = _run(lib, epi, kw, init, 2 | 4)
     fb = _run(lib, epi, kw, init, 2 | 4, dbg=128)   # every tail recomputes its tile
     for k in whole:
@@ -126,9 +133,10 @@ def test_streamk_auto_policy(lib):
     for M, N, expect in ((25800, 1024, 1), (256 * 128, 1024, 0), (12900, 1024, 0)):
         epi, kw = _problem(lib, M, N, 1024, "res", seed=M)
         init = {k: v.clone() for k, v in _outputs(kw).items()}
-        n0 = L.pdm_gemm_sk_launches()
+        n0, p0 = L.pdm_gemm_sk_launches(), SK_PLANNED[0]
         _run(lib, epi, kw, init, 1 | 4)
         assert L.pdm_gemm_sk_launches() - n0 == expect, (M, N)
+        assert SK_PLANNED[0] - p0 == expect, (M, N)
 
 
 def test_streamk_forward_bit_identical(lib):

@@ -378,7 +378,12 @@ def test_gemm_gn_part_policy_mirror(lib, M, N, K, gn_P, epi):
     true -- fused means every partial was written (and is right), not fused means none was."""
     a, w, bias, _, ref = dense_problem(M, N, K, M + N + gn_P)
     part = nan_part(lib.gn_part_elems(M // gn_P, gn_P))
-    out, fused = lib.gemm_gn(a, w, bias, lib.EPI_F32 if epi == "f32" else lib.EPI_BF16, part, gn_P)
+    e = lib.EPI_F32 if epi == "f32" else lib.EPI_BF16
+    pl = lib.gemm_plan(lib.gemm_shape_args(M, N, K, e), e, gn_P=gn_P)
+    out, fused = lib.gemm_gn(a, w, bias, e, part, gn_P)
+    # the entry's answer is the plan's: the epilogue of the planned kernel writes the partials, and their shape rule
+    shape_ok = gn_P % 256 == 0 and M % gn_P == 0 and N % 32 == 0 and N // 32 in (4, 8, 16, 32)
+    assert pl.error is None and bool(fused) == pl.gn_fusable == (pl.writes_gn and shape_ok), (fused, pl)
     check_fused(lib, out, None, part, fused, ref, M // gn_P, gn_P, f"gn_part policy M={M} N={N} gn_P={gn_P} {epi}", None)
     print(f"gn_part policy M={M} N={N} gn_P={gn_P} {epi}: fused = {fused}")
 
@@ -396,6 +401,10 @@ def run_conv_gn(lib, x, w, bias, ref, mode, up, what):
     M, N = B * H * H, w.shape[0]
     part = nan_part(lib.gn_part_elems(B, H * H))
     copy = None
+    e = lib.EPI_BF16 if mode == "bf16" else lib.EPI_F32
+    Cin = x.shape[3]
+    pl = lib.gemm_plan(lib.gemm_shape_args(M, N, 9 * Cin, e, conv_C=Cin, copy=mode == "f32copy", accumulate=mode == "f32acc"),
+                       e, conv=(H, H, Cin, up), gn_P=H * H)
     if mode == "bf16":      # conv1: the partials of the ROUNDED values
         out, fused = lib.gemm_conv3x3_gn(x, w, bias, lib.EPI_BF16, part, up=up)
     elif mode == "f32acc":  # conv2
@@ -405,6 +414,7 @@ def run_conv_gn(lib, x, w, bias, ref, mode, up, what):
     else:                   # the upsample conv: fp32 with the bf16 copy
         copy = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
         out, fused = lib.gemm_conv3x3_gn(x, w, bias, lib.EPI_F32, part, up=up, out=copy)
+    assert pl.error is None and bool(fused) == pl.writes_gn == pl.gn_fusable, (what, fused, pl)
     check_fused(lib, out, copy, part, fused, ref, B, H * H, what, True)
 
 

@@ -69,6 +69,7 @@ def test_c_entry_call_sites_match_sigs():
 
 WRAPPERS = {n: getattr(_lib, n) for n in ("gemm", "rowstats", "gemm_ln", "mx_quantize_gpu", "gemm_ex", "gemm_pair",
                                           "gemm_conv3x3", "gemm_batched", "layernorm", "attention", "attention_plan",
+                                          "gemm_plan",
                                           "lincomb",
                                           "stage_epilogue", "wgrad", "attention_backward", "layernorm_backward",
                                           "mx_quantize", "mx_dequantize", "mx_quantize_centred", "_gemm_args",
@@ -176,6 +177,10 @@ def test_wrappers_marshal_against_fake_library(fake):
         with pytest.raises(ValueError):
             _lib.attention(qkv, 2, 17, 1, 64, out=bad)
     assert _lib.attention_plan(2, 17, 1, 64).family == "streamed"   # the fake leaves out6 zeroed
+    g = _lib._gemm_args(a, w, bias, out=out)
+    pl = _lib.gemm_plan(g, _lib.EPI_BF16, conv=(4, 4, 16, 0), gn_P=256, ncu=256, persist_ok=1)   # out24 zeroed too
+    assert pl.family == "128" and pl.error is None and pl.grouped is False
+    _lib.gemm_plan(g, _lib.EPI_BF16, second=g, sk_attached=True, algo=11)
     _lib.lincomb([torch.randn(8), torch.randn(8)], [1.0, 0.5])
     pre = torch.randn(4, 4, 8, 8)
     _lib.stage_epilogue(pre, 2, conv_w=torch.randn(4, 4, 3, 3), conv_b=torch.randn(4), cfg_scale=0.4,
@@ -228,7 +233,7 @@ def test_wrappers_marshal_against_fake_library(fake):
     p.disable()
     for name in ("pdm_gemm_bf16", "pdm_rowstats", "pdm_gemm_bf16_ln", "pdm_mx_quantize", "pdm_gemm", "pdm_gemm_pair",
                  "pdm_gemm_conv3x3_bf16", "pdm_gemm_batched_bf16", "pdm_layernorm", "pdm_attention",
-                 "pdm_attention_log2", "pdm_attention_plan", "pdm_lincomb", "pdm_stage_epilogue", "pdm_wgrad",
+                 "pdm_attention_log2", "pdm_attention_plan", "pdm_gemm_plan", "pdm_lincomb", "pdm_stage_epilogue", "pdm_wgrad",
                  "pdm_attention_backward",
                  "pdm_layernorm_backward", "pdm_uvit_profile", "pdm_uvit_profile_read", "pdm_wgrad_gather",
                  "pdm_colsum", "pdm_layernorm_backward_rows", "pdm_layernorm_rows", "pdm_gelu_forward",
