@@ -167,7 +167,11 @@ int pdm_uvit_forward(pdm_uvit* h, const float* x, const float* t, const int64_t*
 
 /* replaces UViT(t2i).forward (libs/uvit_t2i.py:378-525).  context [rows, num_clip_token, clip_dim] fp32,
  * mask_token [rows, K, H, W] fp32 or NULL.  Writes eps_pre [rows, C, H, W] and (if mask_token and not
- * use_ground_truth) mask_pre [rows, K, H, W] (pre-final-conv, pre-tanh). */
+ * use_ground_truth) mask_pre [rows, K, H, W] (pre-final-conv, pre-tanh).  A mask token needs enable_panoptic.
+ * separate != 0: the two block stacks with zero-conv injections.  separate == 0 (the reference constructor's default,
+ * the "joint" layout): one stack over [time, context, N image patches, N mask patches] with pos_embed
+ * [extras + 2N, D]; both heads read norm(x), and with use_ground_truth decoder_pred reads norm(x)[image rows] +
+ * norm(x)[mask rows].  Without a mask token either network runs the plain stack over the first extras + N rows. */
 int pdm_uvit_t2i_forward(pdm_uvit* h, const float* x, const float* t, const float* context,
                          const float* mask_token, int use_ground_truth, float* eps_pre, float* mask_pre,
                          int rows, void* workspace, size_t workspace_bytes, void* stream);

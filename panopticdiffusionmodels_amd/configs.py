@@ -11,6 +11,11 @@ Shapes and hyper-parameters are restated from the reference's config files:
     (1 time + 77 context + 1024 patch tokens: image stream 1102, mask stream 2126).  The reference file names no
     panoptic flags, which leaves `separate` at its default False, a branch the port does not carry (the trainer and
     HipNet run the separate streams only); the entry takes the panoptic flags of mscoco_uvit_small instead.
+    The network exactly as the reference file builds it is the mscoco_uvit_small_512_joint entry.
+  * the joint image+mask sequence (`enable_panoptic=True, separate=False`, the constructor's defaults at
+    libs/uvit_t2i.py:259-261): mscoco_uvit_small_joint (mscoco_uvit_small with separate=False),
+    mscoco_uvit_small_512_joint (configs/mscoco_uvit_small_512.py:41-54, 63-70) and mscoco_uvit_large
+    (configs/mscoco_uvit_large.py:41-54, 63-70), the last two with the nnet dict as the file writes it.
 
 `tiny_*` entries are the reduced shapes used for committed golden fixtures.
 """
@@ -154,6 +159,45 @@ CONFIGS = {
         train=dict(batch_size=4, objective="discrete", p_uncond=0.15, ema_rate=0.9),
         optimizer=dict(name="adamw", lr=0.0002, weight_decay=0.03, betas=(0.99, 0.99)),
         lr_scheduler=dict(name="customized", warmup_steps=5),
+    ),
+    # ---- the joint image+mask sequence (enable_panoptic=True, separate=False: one block stack) ----------
+    "tiny_t2i_joint": dict(  # tiny_t2i with separate=False: Dh 32, Lx 70, Lm 134
+        nnet=dict(name="uvit_t2i", img_size=16, in_chans=4, patch_size=2, embed_dim=64, depth=2,
+                  num_heads=2, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=64,
+                  num_clip_token=5, enable_panoptic=True, use_ground_truth=False, separate=False,
+                  num_panoptic_class=8),
+        z_shape=(4, 16, 16), front_end="dpm_solver_pp", cfg_scale=1.0, decode=False,
+        sample_steps=50, mini_batch_size=2, panoptic=True,
+    ),
+    "tiny_t2i_joint64": dict(  # Dh 64 at the full 256^2 token counts: Lx 334, Lm 590
+        nnet=dict(name="uvit_t2i", img_size=32, in_chans=4, patch_size=2, embed_dim=64, depth=2,
+                  num_heads=1, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=64,
+                  num_clip_token=77, enable_panoptic=True, use_ground_truth=False, separate=False,
+                  num_panoptic_class=8),
+        z_shape=(4, 32, 32), front_end="dpm_solver_pp", cfg_scale=1.0, decode=False,
+        sample_steps=50, mini_batch_size=2, panoptic=True,
+    ),
+    "mscoco_uvit_small_joint": dict(  # mscoco_uvit_small with separate=False (Lm 590)
+        nnet=dict(name="uvit_t2i", img_size=32, in_chans=4, patch_size=2, embed_dim=512, depth=12,
+                  num_heads=8, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=768,
+                  num_clip_token=77, enable_panoptic=True, use_ground_truth=False, separate=False,
+                  num_panoptic_class=8),
+        z_shape=(4, 32, 32), front_end="dpm_solver_pp", cfg_scale=1.0, decode=True,
+        scale_factor=0.23010, sample_steps=50, mini_batch_size=32, panoptic=True,
+    ),
+    "mscoco_uvit_small_512_joint": dict(  # configs/mscoco_uvit_small_512.py:41-54 as written (Lm 2126)
+        nnet=dict(name="uvit_t2i", img_size=64, in_chans=4, patch_size=2, embed_dim=512, depth=12,
+                  num_heads=8, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=768,
+                  num_clip_token=77),
+        z_shape=(4, 64, 64), front_end="dpm_solver_pp", cfg_scale=1.0, decode=True,
+        scale_factor=0.23010, sample_steps=50, mini_batch_size=10, panoptic=True,
+    ),
+    "mscoco_uvit_large": dict(  # configs/mscoco_uvit_large.py:41-54, 63-70 as written (Lm 590)
+        nnet=dict(name="uvit_t2i", img_size=32, in_chans=4, patch_size=2, embed_dim=1024, depth=20,
+                  num_heads=16, mlp_ratio=4, qkv_bias=False, mlp_time_embed=False, clip_dim=768,
+                  num_clip_token=77),
+        z_shape=(4, 32, 32), front_end="dpm_solver_pp", cfg_scale=1.0, decode=True,
+        scale_factor=0.23010, sample_steps=50, mini_batch_size=32, panoptic=True,
     ),
 }
 

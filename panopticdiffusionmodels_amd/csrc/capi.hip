@@ -91,6 +91,8 @@ struct pdm_uvit {
   // W norm.bias (+ the Linear's own bias), both fp32 (include/pdm.h)
   // the residual stream is bf16 (cfg.residual_fp32 == 0)
   bool res16() const { return !cfg.residual_fp32; }
+  // the joint image+mask sequence (libs/uvit_t2i.py with enable_panoptic and separate=False): one block stack
+  bool joint() const { return cfg.t2i && cfg.enable_panoptic && !cfg.separate; }
   // block Linear `bit` (0 qkv, 1 proj, 2 fc1, 3 fc2) runs in MXFP8 (cfg.fp8 / cfg.fp8_linears)
   bool f8(int bit) const { return cfg.fp8 && (((cfg.fp8_linears ? cfg.fp8_linears : 0xF) >> bit) & 1); }
   // a block Linear's weight [N][K]: bf16, or (MXFP8) e4m3 bytes + "<key>_scale" E8M0 dwords [K/128][N]; an MXFP8
@@ -137,7 +139,7 @@ struct Q8 {
 
 // workspace layout
 struct Workspace {
-  float* X;     // [rows*Lx, D] residual stream (image)
+  float* X;     // [rows*Lx, D] residual stream (image); a joint net (t2i, separate=False): [rows*Lm, D] here, in XB / SK
   bf16* XB;     // [rows*Lx, D] bf16 copy of x (qkv / skip_linear A operand)
   bf16* XT;     // [rows*Lmax, D] bf16 copy of the block-internal x (after skip_linear / attention)
   float* ST;    // [rows*Lmax, T] (sum, M2) LayerNorm partials of x at block entry / exit, T = ceil(D/256)
@@ -146,7 +148,7 @@ struct Workspace {
   bf16* ATT;    // [rows*Lmax, D]
   bf16* MLP;    // [rows*Lmax, Hid]
   bf16* SK;     // [nhalf][rows*Lx, D] long-skip activations (image)
-  bf16* HEADIN; // [rows*n_patch, D]
+  bf16* HEADIN; // [rows*n_patch, D]; a joint net: [rows*2*n_patch, D] (image rows, then mask rows, per sample)
   // t2i
   float* CTXF;  // [rows*n_ctx, D] embedded context (fp32)
   bf16* CTXB;   // [rows*n_ctx, clip_dim] bf16 context
@@ -177,7 +179,10 @@ Workspace layout(const pdm_uvit* h, int rows, char* base) {
     return p;
   };
   const size_t D = h->D;
-  const size_t Mx = (size_t)rows * h->Lx;
+  // a joint net runs its one stack over [time, context, image patches, mask patches]: every buffer of the single
+  // stream holds Lm rows per sample, the head input both patch halves, and there is no mask stream
+  const bool joint = h->joint();
+  const size_t Mx = (size_t)rows * (joint ? h->Lm : h->Lx);
   const bool mask = h->cfg.t2i && h->cfg.separate && h->cfg.enable_panoptic;
   const size_t Mm = mask ? (size_t)rows * h->Lm : 0;
   const size_t Mmax = Mx > Mm ? Mx : Mm;
@@ -192,7 +197,7 @@ Workspace layout(const pdm_uvit* h, int rows, char* base) {
   w.ATT = (bf16*)take(Mmax * D * 2);
   if (!f8) w.MLP = (bf16*)take(Mmax * h->Hid * 2);
   w.SK = (bf16*)take((size_t)h->nhalf * Mx * D * 2);
-  w.HEADIN = (bf16*)take((size_t)rows * h->n_patch * D * 2);
+  w.HEADIN = (bf16*)take((size_t)rows * (joint ? 2 : 1) * h->n_patch * D * 2);
   if (f8) {
     auto q8 = [&](size_t K) {
       Q8 r;
@@ -1021,8 +1026,6 @@ int pdm_uvit_create(const pdm_uvit_cfg* cfg, pdm_uvit** out) {
   if (c.mlp_time_embed) return fail(PDM_ERR_ARG, "mlp_time_embed=True is not supported by the HIP path");
   if (c.embed_dim % 64) return fail(PDM_ERR_ARG, "embed_dim must be a multiple of 64");
   if (c.mlp_hidden % 64) return fail(PDM_ERR_ARG, "mlp hidden size must be a multiple of 64");
-  if (c.t2i && c.enable_panoptic && !c.separate)
-    return fail(PDM_ERR_ARG, "uvit_t2i with enable_panoptic and separate=False is not supported by the HIP path");
   if (c.fp8 && c.t2i) return fail(PDM_ERR_ARG, "fp8: only the class-conditional / unconditional U-ViT has an MXFP8 path");
   if (c.fp8 && (c.embed_dim % 128 || c.mlp_hidden % 128))
     return fail(PDM_ERR_ARG, "fp8: embed_dim and the mlp hidden size must be multiples of 128 (MXFP8 K-tiles)");
@@ -1062,7 +1065,7 @@ int pdm_uvit_create(const pdm_uvit_cfg* cfg, pdm_uvit** out) {
   h->Lm = h->Lx + h->n_patch;
   const int D = h->D;
   const int pk = c.in_chans * c.patch_size * c.patch_size;
-  h->add("pos_embed", PDM_F32, (long long)h->Lx * D);
+  h->add("pos_embed", PDM_F32, (long long)(h->joint() ? h->Lm : h->Lx) * D);   // joint: rows [Lx, Lm) = mask patches
   h->add("patch_embed.proj.weight", PDM_F32, (long long)D * pk);
   h->add("patch_embed.proj.bias", PDM_F32, D);
   if (!c.t2i && c.num_classes > 0) h->add("label_emb.weight", PDM_F32, (long long)c.num_classes * D);
@@ -1091,6 +1094,12 @@ int pdm_uvit_create(const pdm_uvit_cfg* cfg, pdm_uvit** out) {
       h->add(zc + ".weight", PDM_BF16, (long long)D * D);
       h->add(zc + ".bias", PDM_F32, D);
     }
+  }
+  if (h->joint()) {   // one stack: the mask patches' embedding and head only (mask_embed_0 is unused: 392-396)
+    h->add("mask_embed.proj.weight", PDM_F32, (long long)D * h->PK);
+    h->add("mask_embed.proj.bias", PDM_F32, D);
+    h->add("decoder_pred_mask.weight", PDM_BF16, (long long)h->PK_pad * D);
+    h->add("decoder_pred_mask.bias", PDM_F32, h->PK);
   }
   *out = h;
   return PDM_OK;
@@ -1211,9 +1220,12 @@ int pdm_uvit_t2i_forward(pdm_uvit* h, const float* x, const float* t, const floa
                          size_t workspace_bytes, void* stream) {
   if (!h || !x || !t || !context || !eps_pre || rows <= 0) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: bad argument");
   if (!h->cfg.t2i) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: not a t2i network");
-  const bool two = mask_token && h->cfg.separate && h->cfg.enable_panoptic;
-  if (mask_token && !two) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: mask tokens need enable_panoptic and separate");
-  if (two && !use_ground_truth && !mask_pre) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: mask_pre output missing");
+  if (mask_token && !h->cfg.enable_panoptic)
+    return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: mask tokens need a network built with enable_panoptic");
+  const bool two = mask_token && h->cfg.separate;     // two block stacks with zero-conv injections
+  const bool joint = mask_token && !h->cfg.separate;  // one stack over [time, context, image patches, mask patches]
+  if (mask_token && !use_ground_truth && !mask_pre)
+    return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: mask tokens without use_ground_truth need the mask_pre output");
   PDM_TRY(check_ready(h));
   Workspace w = layout(h, rows, (char*)workspace);
   if (w.bytes > workspace_bytes) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: workspace too small");
@@ -1232,12 +1244,48 @@ int pdm_uvit_t2i_forward(pdm_uvit* h, const float* x, const float* t, const floa
     a.patch_w = h->f("patch_embed.proj.weight"); a.patch_b = h->f("patch_embed.proj.bias");
     a.t = t; a.ctx_tokens = w.CTXF; a.n_ctx = nctx;
     a.pos = h->f("pos_embed");
-    a.out = w.X; a.ld_out = D; a.B = rows; a.D = D; a.L_total = Lx;
+    // (joint: the first Lx rows of each Lm-row sequence; either way only pos_embed rows [0, Lx) are read)
+    a.out = w.X; a.ld_out = D; a.B = rows; a.D = D; a.L_total = joint ? Lm : Lx;
     a.row0_patch = h->extras; a.time_row = 0; a.label_row = -1; a.ctx_row = 1;
     PDM_CHECK(pdm::assemble_check(a));
     PDM_HIP(pdm::assemble_launch(a, c.s));
   }
   const size_t MDx = (size_t)rows * Lx * D;
+  if (joint) {  // separate=False (397-399, 419-520): the single stack over all Lm rows, both heads on norm(x)
+    const int N = h->n_patch;
+    {  // mask patches mask_embed(mask_token) + pos_embed[Lx:Lm] -> rows [Lx, Lm) of each sequence
+      pdm::AssembleArgs a{};
+      a.img = mask_token; a.C = h->K; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
+      a.patch_w = h->f("mask_embed.proj.weight"); a.patch_b = h->f("mask_embed.proj.bias");
+      a.pos = h->f("pos_embed") + (size_t)Lx * D;
+      a.out = w.X + (size_t)Lx * D; a.ld_out = D; a.B = rows; a.D = D; a.L_total = Lm;
+      a.row0_patch = 0; a.time_row = -1; a.label_row = -1; a.ctx_row = -1;
+      PDM_CHECK(pdm::assemble_check(a));
+      PDM_HIP(pdm::assemble_launch(a, c.s));
+    }
+    if (h->res16()) PDM_TRY(run_stack16(c, w, rows, Lm));
+    else PDM_TRY(run_stack(c, w, rows, Lm));
+    // final norm over the 2N patch rows only (rows [extras, Lm) of each sequence) -> HEADIN [rows][2N][D]; with
+    // use_ground_truth the image row and its mask row are normalised and summed in one pass -> HEADIN [rows][N][D]
+    pdm::LayerNormArgs a{};
+    if (h->res16()) a.xb = w.XB; else a.x = w.X;
+    a.ldx = D;
+    a.gamma = h->f("norm.weight"); a.beta = h->f("norm.bias");
+    a.y = w.HEADIN; a.ldy = D; a.D = D;
+    a.group_stride = Lm; a.row_offset = h->extras;
+    a.eps = 1e-5f;
+    if (use_ground_truth) {
+      a.rows = rows * N; a.rows_per_group = N; a.pair_offset = N;
+    } else {
+      a.rows = rows * 2 * N; a.rows_per_group = 2 * N;
+    }
+    PDM_CHECK(pdm::layernorm_check(a));
+    PDM_HIP(pdm::layernorm_launch(a, c.s));
+    if (use_ground_truth)
+      return run_head(c, w.HEADIN, N, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre);
+    PDM_TRY(run_head(c, w.HEADIN, 2 * N, N, rows, "decoder_pred_mask", h->K, h->PK, h->PK_pad, mask_pre));
+    return run_head(c, w.HEADIN, 2 * N, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre);
+  }
   if (!two) {  // plain text-conditioned U-ViT (mask_token None: 407-410, 516-517)
     if (h->res16()) {
       PDM_TRY(run_stack16(c, w, rows, Lx));

@@ -70,6 +70,73 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LayerNormArgs p) {
   }
 }
 
+// Sum of two normalised rows of one stream (LayerNormArgs::pair_offset; the joint t2i ground-truth tail,
+// libs/uvit_t2i.py:486-496: decoder_pred(norm(x)[image rows] + norm(x)[mask rows])): one wave per output row holds
+// row `src` and row `src + pair_offset` in registers, normalises each with its own mean / rstd (two-pass, as
+// layernorm_kernel), adds the two affine results in fp32 and rounds the sum once to bf16.
+template <int NV>
+__device__ __forceinline__ float ln_load_row(const LayerNormArgs& p, int src, int lane, int nv, f32x4 (&v)[NV]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int idx = lane + i * 64;
+    if (idx < nv) {
+      if (p.xb) {
+        const bf16x4 b = reinterpret_cast<const bf16x4*>(p.xb + (size_t)src * p.ldx)[idx];
+        v[i] = f32x4{(float)b[0], (float)b[1], (float)b[2], (float)b[3]};
+      } else {
+        v[i] = reinterpret_cast<const f32x4*>(p.x + (size_t)src * p.ldx)[idx];
+      }
+      s += (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+    }
+  }
+  return s;
+}
+
+template <int NV>
+__device__ __forceinline__ float ln_sq_dev(const f32x4 (&v)[NV], float mean, int lane, int nv) {
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int idx = lane + i * 64;
+    if (idx < nv) {
+      const f32x4 d = v[i] - mean;
+      q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+    }
+  }
+  return q;
+}
+
+template <int NV>
+__global__ __launch_bounds__(256) void layernorm_pairsum_kernel(LayerNormArgs p) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r = blockIdx.x * 4 + wave;
+  if (r >= p.rows) return;
+  const int src = (r / p.rows_per_group) * p.group_stride + p.row_offset + (r % p.rows_per_group);
+  const int nv = p.D >> 2;
+  f32x4 va[NV], vb[NV];
+  const float sa = ln_load_row<NV>(p, src, lane, nv, va);
+  const float sb = ln_load_row<NV>(p, src + p.pair_offset, lane, nv, vb);
+  const float mean_a = wave_sum(sa) / (float)p.D;
+  const float mean_b = wave_sum(sb) / (float)p.D;
+  const float rstd_a = 1.0f / sqrtf(wave_sum(ln_sq_dev<NV>(va, mean_a, lane, nv)) / (float)p.D + p.eps);
+  const float rstd_b = 1.0f / sqrtf(wave_sum(ln_sq_dev<NV>(vb, mean_b, lane, nv)) / (float)p.D + p.eps);
+  const f32x4* gm = reinterpret_cast<const f32x4*>(p.gamma);
+  const f32x4* bt = reinterpret_cast<const f32x4*>(p.beta);
+  bf16x4* y = reinterpret_cast<bf16x4*>(p.y + (size_t)r * p.ldy);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int idx = lane + i * 64;
+    if (idx < nv) {
+      const f32x4 g = gm[idx], b = bt[idx];
+      const f32x4 oa = (va[i] - mean_a) * rstd_a * g + b;
+      const f32x4 ob = (vb[i] - mean_b) * rstd_b * g + b;
+      const f32x4 o = oa + ob;
+      y[idx] = to_bf16x4(o[0], o[1], o[2], o[3]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------
 // LayerNorm row partials for the fused LayerNorm (see GemmArgs): one wave per row; float4 chunk i of the row
 // covers columns 256 i .. 256 i + 255, i.e. exactly one partial group, so each group is two wave sums.
@@ -453,11 +520,29 @@ const char* layernorm_check(const LayerNormArgs& p) {
   if (p.ldx % 4 || p.ldy % 4) return "layernorm: row strides must be multiples of 4";
   if (p.rows_per_group <= 0) return "layernorm: rows_per_group must be positive";
   if ((!p.x && !p.xb) || !p.gamma || !p.beta || !p.y) return "layernorm: null pointer";
+  if (p.pair_offset < 0) return "layernorm: pair_offset must be >= 0";
+  if (p.pair_offset > 0) {   // both rows of a pair lie inside their own group (sequence) of the input
+    if (p.add || p.addb) return "layernorm: pair_offset excludes add / addb";
+    if (p.row_offset < 0 || p.row_offset + p.rows_per_group + p.pair_offset > p.group_stride)
+      return "layernorm: the paired rows must lie inside group_stride";
+  }
   return nullptr;
 }
 
 hipError_t layernorm_launch(const LayerNormArgs& p, hipStream_t stream) {
   const dim3 grid((p.rows + 3) / 4), block(256);
+  if (p.pair_offset > 0) {
+    switch ((p.D / 4 + 63) / 64) {
+      case 1: hipLaunchKernelGGL(layernorm_pairsum_kernel<1>, grid, block, 0, stream, p); break;
+      case 2: hipLaunchKernelGGL(layernorm_pairsum_kernel<2>, grid, block, 0, stream, p); break;
+      case 3: hipLaunchKernelGGL(layernorm_pairsum_kernel<3>, grid, block, 0, stream, p); break;
+      case 4: hipLaunchKernelGGL(layernorm_pairsum_kernel<4>, grid, block, 0, stream, p); break;
+      case 5: hipLaunchKernelGGL(layernorm_pairsum_kernel<5>, grid, block, 0, stream, p); break;
+      case 6: hipLaunchKernelGGL(layernorm_pairsum_kernel<6>, grid, block, 0, stream, p); break;
+      default: hipLaunchKernelGGL(layernorm_pairsum_kernel<8>, grid, block, 0, stream, p); break;
+    }
+    return hipGetLastError();
+  }
   switch ((p.D / 4 + 63) / 64) {
     case 1: hipLaunchKernelGGL(layernorm_kernel<1>, grid, block, 0, stream, p); break;
     case 2: hipLaunchKernelGGL(layernorm_kernel<2>, grid, block, 0, stream, p); break;

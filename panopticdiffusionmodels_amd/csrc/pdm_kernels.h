@@ -171,6 +171,9 @@ struct LayerNormArgs {
   const float* add;           // optional fp32 rows added after the affine (gathered like x, with add_* below)
   const bf16* addb;           // the same rows in bf16 (the bf16 residual stream), instead of add
   int add_ld, add_group_stride, add_row_offset;
+  // > 0: y row r = bf16(LN(input row) + LN(input row + pair_offset)), both with gamma / beta, summed in fp32 and
+  // rounded once (the joint t2i ground-truth tail: image row + mask row of one sequence); excludes add / addb
+  int pair_offset;
 };
 const char* layernorm_check(const LayerNormArgs& p);
 hipError_t layernorm_launch(const LayerNormArgs& p, hipStream_t stream);

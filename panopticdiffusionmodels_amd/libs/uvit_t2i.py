@@ -4,6 +4,9 @@ Keeps the reference constructor and state_dict keys.  With `separate=True` and a
 runs the two block stacks of the reference (image stream over [time, context, patches]; mask stream over
 mx = cat(x, m) with zero-initialised 1x1 `zeroconv` injections back into the image stream) as one native
 call (pdm_uvit_t2i_forward); the heads, final convs, tanh and CFG are applied by pdm_stage_epilogue.
+With `separate=False` (the constructor's default) the same call runs the reference's joint layout: one block
+stack over [time, context, image patches, mask patches] with a `pos_embed` of extras + 2 N rows, and both heads
+on the normalised rows.
 """
 import torch
 import torch.nn as nn
@@ -119,9 +122,8 @@ class UViT(HipNet):
             context = context.expand(B, -1, -1).contiguous()
         mt = None
         if mask_token is not None:
-            if not (self.enable_panoptic and self.separate):
-                raise NotImplementedError("mask tokens are supported for separate=True networks (the BASELINE "
-                                          "panoptic config); separate=False is not on the HIP path")
+            if not self.enable_panoptic:
+                raise ValueError("mask tokens need a network built with enable_panoptic=True")
             mt = mask_token.to(device=x.device, dtype=torch.float32).contiguous()
         if out is None:
             out = torch.empty(B, self.in_chans, self.img_size, self.img_size, device=x.device)
