@@ -94,7 +94,8 @@ def uvit_forward(sd, cfg, x, timesteps, y=None):
         skips.append(x)
     x = block(sd, "mid_block", x, heads)
     for i in range(depth // 2):
-        x = block(sd, f"out_blocks.{i}", x, heads, skip=skips.pop())
+        skip = skips.pop()  # skip=False: the out-blocks have no skip_linear and ignore it (libs/uvit.py:116)
+        x = block(sd, f"out_blocks.{i}", x, heads, skip=skip if cfg.get("skip", True) else None)
     x = F.layer_norm(x, (D,), sd["norm.weight"], sd["norm.bias"], eps=1e-5)
     x = F.linear(x, sd["decoder_pred.weight"], sd["decoder_pred.bias"])
     assert x.shape[1] == extras + L

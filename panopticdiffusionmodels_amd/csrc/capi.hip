@@ -62,6 +62,29 @@ struct ParamSpec {
   const void* ptr = nullptr;
 };
 
+// Registered weights resolved to pointers (pdm_uvit::resolve), so a forward builds no key and searches no map.
+// One Linear: weight, bias (a LayerNorm consumer's ln_bias) and, where registered, ln_colsum, the MXFP8 weight's
+// "_scale" and the consumer's ln_gcol; null where the network has none.
+struct LinW {
+  const bf16* w = nullptr;
+  const float* bias = nullptr;
+  const float* colsum = nullptr;
+  const unsigned* scale = nullptr;
+  const bf16* gcol = nullptr;
+};
+struct BlockW {
+  LinW qkv, proj, fc1, fc2, skip;   // skip.w null: no long skip
+};
+// One layer of the in / mid / out walk (libs/uvit.py:213-222): its image block, its mask block and zero-conv (a
+// `separate` panoptic net, libs/uvit_t2i.py:411-472), and the long-skip wiring, fixed at create time.
+struct Layer {
+  BlockW img, mask;
+  LinW zc;
+  int keep = -1;        // in-block i: its output is kept in long-skip slot i
+  int skip_from = -1;   // out-block with a long skip: the slot its skip_linear reads
+  bool last = false;    // the last out-block
+};
+
 }  // namespace
 
 struct pdm_uvit {
@@ -69,6 +92,12 @@ struct pdm_uvit {
   int D, H, Dh, Hid, C, p, n_patch, extras, Lx, Lm, P, P_pad, K, PK, PK_pad, depth, nhalf;
   std::vector<std::string> order;
   std::map<std::string, ParamSpec> params;
+  // the resolved table: rebuilt by check_ready after pdm_uvit_set_param (dirty)
+  bool dirty = true;
+  std::vector<Layer> layers;
+  LinW ctx_embed, head, head_mask;
+  const float *pos = nullptr, *pos_mask = nullptr, *patch_w = nullptr, *patch_b = nullptr, *mask_w = nullptr,
+              *mask_b = nullptr, *label_emb = nullptr, *norm_w = nullptr, *norm_b = nullptr;
   // profiling hook: events around every GEMM launch of the last forward (bench roofline)
   mutable std::vector<hipEvent_t> prof_ev;
   mutable std::vector<double> prof_flops;
@@ -118,9 +147,47 @@ struct pdm_uvit {
     add_lin(pre + ".mlp.fc2.weight", D, Hid, 3, false);
     add(pre + ".mlp.fc2.bias", PDM_F32, D);
     if (skip) {
-      add(pre + ".skip_linear.weight", PDM_BF16, 2LL * D * D);   // bf16 in both modes (run_block8)
+      add(pre + ".skip_linear.weight", PDM_BF16, 2LL * D * D);   // bf16 also in an MXFP8 net (run_block)
       add(pre + ".skip_linear.bias", PDM_F32, D);
     }
+  }
+  // state_dict prefix of layer l's block: in_blocks.i, mid_block, out_blocks.i (+ "_mask": the mask stream's)
+  std::string block_name(int l, const char* sfx) const {
+    if (l == nhalf) return std::string("mid_block") + sfx;
+    return (l < nhalf ? "in_blocks" : "out_blocks") + std::string(sfx) + "." + std::to_string(l < nhalf ? l : l - nhalf - 1);
+  }
+  static std::string zc_name(int l) { return "zero_convs." + std::to_string(2 * l + 1) + ".conv"; }
+  void add_stack(const char* sfx) {
+    for (int l = 0; l <= 2 * nhalf; ++l) add_block(block_name(l, sfx), l > nhalf && cfg.skip);
+  }
+  void resolve() {
+    auto lin = [&](const std::string& p, bool ln = false) {
+      LinW l;
+      l.w = w(p + ".weight");
+      l.bias = f(p + (ln ? ".ln_bias" : ".bias"));
+      l.colsum = f(p + ".ln_colsum");
+      l.scale = static_cast<const unsigned*>(ptr(p + ".weight_scale"));
+      l.gcol = w(p + ".ln_gcol");
+      return l;
+    };
+    auto block = [&](const std::string& pre) {
+      return BlockW{lin(pre + ".attn.qkv", true), lin(pre + ".attn.proj"), lin(pre + ".mlp.fc1", true),
+                    lin(pre + ".mlp.fc2"), lin(pre + ".skip_linear")};
+    };
+    for (int l = 0; l < (int)layers.size(); ++l) {
+      layers[l].img = block(block_name(l, ""));
+      layers[l].mask = block(block_name(l, "_mask"));
+      layers[l].zc = lin(zc_name(l));
+    }
+    ctx_embed = lin("context_embed");
+    head = lin("decoder_pred");
+    head_mask = lin("decoder_pred_mask");
+    pos = f("pos_embed"); pos_mask = f("pos_embed_mask");
+    patch_w = f("patch_embed.proj.weight"); patch_b = f("patch_embed.proj.bias");
+    mask_w = f("mask_embed.proj.weight"); mask_b = f("mask_embed.proj.bias");
+    label_emb = f("label_emb.weight");
+    norm_w = f("norm.weight"); norm_b = f("norm.bias");
+    dirty = false;
   }
 };
 
@@ -159,7 +226,7 @@ struct Workspace {
   bf16* SKM;    // [nhalf][rows*Lm, D]
   float* STM;   // [rows*Lm, T] LayerNorm partials of the mask stream
   // t2i on the bf16 stream: the image block's own scratch, so it runs in lockstep with the mask block of its layer
-  // (every block Linear of the pair one grouped launch, run_block16_pair)
+  // (every block Linear of the pair one grouped launch, run_block on two streams)
   bf16 *XT2, *QKV2, *ATT2, *MLP2;
   float* STT2;
   // fp8 forward (cfg.fp8): MXFP8 operands of the block Linears, e4m3 rows + E8M0 scale dwords [K/128][rows*Lx]
@@ -243,6 +310,7 @@ struct Ctx {
   unsigned* skf = nullptr;
   float* sks = nullptr;
   int* skn = nullptr;
+  int sk_used = 0;   // what skn counts in (begin_forward)
 };
 
 // Stream-K state of the persistent GEMM (pdm::GemmArgs::sk_flags / sk_slab): SK_RING blocks of SK_FLAG_WORDS flag
@@ -302,13 +370,6 @@ int sk_begin(Ctx& c, int* counter) {
   return PDM_OK;
 }
 
-// fused-LayerNorm operands of one GEMM: partials produced (st_out) or consumed (st_in + colsum)
-struct LnIO {
-  float* st_out = nullptr;
-  const float* st_in = nullptr;
-  const float* colsum = nullptr;
-};
-
 // checked launch + the profiling hook (HIP events around every GEMM of the forward)
 int launch_gemm(const Ctx& c, const pdm::GemmArgs& a, int epi) {
   PDM_CHECK(pdm::gemm_check(a, epi));
@@ -327,52 +388,6 @@ int launch_gemm(const Ctx& c, const pdm::GemmArgs& a, int epi) {
     ++h->prof_n;
   }
   return PDM_OK;
-}
-
-int gemm(const Ctx& c, const bf16* A, int lda, const bf16* W, const float* bias, int M, int N, int K, int epi,
-         bf16* ob, int ldo, float* of, int ldr, int accumulate, const bf16* A2 = nullptr, int lda2 = 0, int K1 = 0,
-         int a_rpg = 0, int a_gs = 0, LnIO ln = LnIO()) {
-  pdm::GemmArgs a{};
-  const int T = (c.h->D + 255) / 256;
-  a.stats_out = ln.st_out; a.stats_ld = T;
-  a.ln_stats = ln.st_in; a.ln_ld = T; a.ln_D = K; a.ln_eps = 1e-5f; a.ln_colsum = ln.colsum;
-  a.A1 = A; a.lda1 = lda;
-  a.A2 = A2; a.lda2 = lda2;
-  a.K1 = A2 ? K1 : K;
-  a.W = W; a.bias = bias;
-  a.M = M; a.N = N; a.K = K;
-  a.out_bf16 = ob; a.ldo = ldo;
-  a.out_f32 = of; a.ldr = ldr;
-  a.accumulate = accumulate;
-  a.a_rows_per_group = a_rpg; a.a_group_stride = a_gs;
-  return launch_gemm(c, a, epi);
-}
-
-// GemmArgs of a bf16 block Linear: the fused-LayerNorm consumer (ln.st_in, bf16 / GELU epilogue) or the bf16 residual
-// epilogue (EPI_RES: out = bf16(A W^T + bias (+ res_in)), partials st_out; A2 = the split-K long-skip operand)
-pdm::GemmArgs ln_args(const pdm_uvit* h, const bf16* A, const bf16* W, const float* bias, int M, int N, int K, bf16* out,
-                      const float* st_in, const float* colsum) {
-  pdm::GemmArgs a{};
-  const int T = (h->D + 255) / 256;
-  a.ln_stats = st_in; a.ln_ld = T; a.ln_D = K; a.ln_eps = 1e-5f; a.ln_colsum = colsum; a.stats_ld = T;
-  a.A1 = A; a.lda1 = K; a.K1 = K;
-  a.W = W; a.bias = bias;
-  a.M = M; a.N = N; a.K = K;
-  a.out_bf16 = out; a.ldo = N;
-  return a;
-}
-pdm::GemmArgs res_args(const bf16* A, int lda, const bf16* W, const float* bias, int M, int N, int K, const bf16* res_in,
-                       bf16* out, float* st_out, const bf16* A2 = nullptr, int lda2 = 0, int K1 = 0) {
-  pdm::GemmArgs a{};
-  a.A1 = A; a.lda1 = lda;
-  a.A2 = A2; a.lda2 = lda2;
-  a.K1 = A2 ? K1 : K;
-  a.W = W; a.bias = bias;
-  a.M = M; a.N = N; a.K = K;
-  a.out_bf16 = out; a.ldo = N;
-  a.res_in = res_in; a.ldri = N; a.accumulate = res_in ? 1 : 0;
-  a.stats_out = st_out; a.stats_ld = (N + 255) / 256;
-  return a;
 }
 
 // two GEMMs as one grouped launch where the kernel takes both (pdm::gemm_launch_pair), with the profiling hook
@@ -397,224 +412,179 @@ int launch_gemm_pair(const Ctx& c, const pdm::GemmArgs& a, const pdm::GemmArgs& 
   return PDM_OK;
 }
 
-// MXFP8 block Linear (cfg.fp8): A and the weight `wkey` (+ "<wkey>_scale") on the block-scaled MFMA; the
-// epilogue also writes the MXFP8 copy of what it stores into `out` when out.q is set (the next Linear's operand)
-// LayerNorm consumers (ln.st_in) take their A operand group-centred (GemmArgs::ln_gcol, "<lin>.ln_gcol"); an
-// MXFP8 output written beside LayerNorm partials (ln.st_out) is group-centred (GemmArgs::mx_center).
-// epi == EPI_RES: the bf16 residual stream, res_in (may alias ob) added when accumulate.
-int gemm8(const Ctx& c, const Q8& A, const std::string& wkey, const float* bias, int M, int N, int K, int epi,
-          bf16* ob, float* of, int accumulate, LnIO ln, const Q8& out, const bf16* res_in = nullptr) {
-  const pdm_uvit* h = c.h;
+// How a forward runs its blocks ("forward orchestration"):
+//   r16: the residual stream x is bf16 (cfg.residual_fp32 == 0): the residual Linears take EPI_RES, out = bf16(A W^T
+//        + bias (+ x)), and x lives in bf16 buffers; else x is fp32 in X, they take EPI_F32 (X (+)= ...) and leave a
+//        bf16 copy for the next bf16 operand
+//   f8:  which block Linears are MXFP8, bit 0 qkv, 1 proj, 2 fc1, 3 fc2 (0: none; pdm_uvit_create admits 0xF and
+//        0xB, so qkv, proj and fc2 go together)
+struct Mode {
+  bool r16;
+  int f8;
+};
+Mode mode_of(const pdm_uvit* h) {
+  return Mode{h->res16(), h->cfg.fp8 ? (h->cfg.fp8_linears ? h->cfg.fp8_linears : 0xF) : 0};
+}
+
+// GemmArgs of a LayerNorm-consuming block Linear (qkv, fc1; norm1 / norm2 folded into the weight, see pdm_uvit):
+// out = epi(LN(x) W^T + bias) from bf16 x [M][K] and its partials st_in
+pdm::GemmArgs ln_lin(const pdm_uvit* h, const bf16* A, const LinW& lw, int M, int N, int K, bf16* out,
+                     const float* st_in) {
   pdm::GemmArgs a{};
   const int T = (h->D + 255) / 256;
-  a.stats_out = ln.st_out; a.stats_ld = T;
-  a.ln_stats = ln.st_in; a.ln_ld = T; a.ln_D = K; a.ln_eps = 1e-5f; a.ln_colsum = ln.colsum;
-  if (ln.st_in) a.ln_gcol = h->w(wkey.substr(0, wkey.size() - 7) + ".ln_gcol");
-  a.mx_center = out.q && ln.st_out ? 1 : 0;
-  a.A1 = (const bf16*)A.q; a.lda1 = A.ld; a.K1 = K;
-  a.W = (const bf16*)h->ptr(wkey); a.bias = bias;
-  a.M = M; a.N = N; a.K = K;
-  a.out_bf16 = ob; a.ldo = ob ? N : 0;
-  a.out_f32 = of; a.ldr = of ? h->D : 0; a.accumulate = accumulate;
-  a.fp8 = 1;
-  a.a_scale = A.s; a.a_scale_ld = A.sld;
-  a.w_scale = (const unsigned*)h->ptr(wkey + "_scale"); a.w_scale_ld = N;
-  a.out_fp8 = out.q; a.ldo8 = out.ld; a.out_scale = out.s; a.out_scale_ld = out.sld;
-  a.res_in = res_in; a.ldri = res_in ? N : 0;
-  return launch_gemm(c, a, epi);
-}
-
-// One U-ViT Block (libs/uvit.py:115-120) on `rows_L` token rows of width D held in X (fp32), with norm1 /
-// norm2 fused into qkv / fc1 (GemmArgs): on entry xb_in = bf16(X) and st_in = the LayerNorm partials of X;
-// the producing epilogues (skip_linear, proj, fc2) leave bf16(x) and its partials for the next consumer.
-//   skip_in:          bf16 [rows_L, D] long-skip activation (out-blocks)
-//   xb_out / st_out:  where fc2's epilogue writes bf16 of the block output and its partials (either may be null)
-int run_block(const Ctx& c, const std::string& pre, float* X, int nseq, int L, const bf16* xb_in, const float* st_in,
-              const bf16* skip_in, bf16* xb_out, float* st_out, const Workspace& w) {
-  const pdm_uvit* h = c.h;
-  const int D = h->D, M = nseq * L;
-  const bf16* xb = xb_in;
-  const float* st = st_in;
-  if (skip_in) {  // x = skip_linear(cat([x, skip], -1)): split-K over the two bf16 operands
-    LnIO io;
-    io.st_out = w.STT;
-    PDM_TRY(gemm(c, xb_in, D, h->w(pre + ".skip_linear.weight"), h->f(pre + ".skip_linear.bias"), M, D, 2 * D,
-                 pdm::EPI_F32, w.XT, D, X, D, 0, skip_in, D, D, 0, 0, io));
-    xb = w.XT;
-    st = w.STT;
-  }
-  {  // qkv = norm1(x) W^T
-    LnIO io;
-    io.st_in = st;
-    io.colsum = h->f(pre + ".attn.qkv.ln_colsum");
-    PDM_TRY(gemm(c, xb, D, h->w(pre + ".attn.qkv.weight"), h->f(pre + ".attn.qkv.ln_bias"), M, 3 * D, D,
-                 pdm::EPI_BF16, w.QKV, 3 * D, nullptr, 0, 0, nullptr, 0, 0, 0, 0, io));
-  }
-  {
-    pdm::AttentionArgs a{};
-    a.qkv = w.QKV; a.ldq = 3 * D;
-    a.out = w.ATT; a.ldo = D;
-    a.B = nseq; a.L = L; a.H = h->H; a.Dh = h->Dh;
-    a.scale = 1.0f / sqrtf((float)h->Dh);
-    a.q_log2 = 1;   // attn.qkv's q rows are packed pre-scaled by Dh^-0.5 log2(e) (include/pdm.h)
-    PDM_CHECK(pdm::attention_check(a));
-    PDM_HIP(pdm::attention_launch(a, c.s));
-  }
-  {  // x += proj(attn)
-    LnIO io;
-    io.st_out = w.STT;
-    PDM_TRY(gemm(c, w.ATT, D, h->w(pre + ".attn.proj.weight"), h->f(pre + ".attn.proj.bias"), M, D, D, pdm::EPI_F32,
-                 w.XT, D, X, D, 1, nullptr, 0, 0, 0, 0, io));
-  }
-  {  // h = GELU(fc1(norm2(x)))
-    LnIO io;
-    io.st_in = w.STT;
-    io.colsum = h->f(pre + ".mlp.fc1.ln_colsum");
-    PDM_TRY(gemm(c, w.XT, D, h->w(pre + ".mlp.fc1.weight"), h->f(pre + ".mlp.fc1.ln_bias"), M, h->Hid, D,
-                 pdm::EPI_GELU, w.MLP, h->Hid, nullptr, 0, 0, nullptr, 0, 0, 0, 0, io));
-  }
-  {  // x += fc2(h)
-    LnIO io;
-    io.st_out = st_out;
-    PDM_TRY(gemm(c, w.MLP, h->Hid, h->w(pre + ".mlp.fc2.weight"), h->f(pre + ".mlp.fc2.bias"), M, D, h->Hid,
-                 pdm::EPI_F32, xb_out, D, X, D, 1, nullptr, 0, 0, 0, 0, io));
-  }
-  return PDM_OK;
-}
-
-// Residual GEMM on the bf16 residual stream (EPI_RES): out = bf16(A W^T + bias (+ res_in)) and its LayerNorm
-// partials (st_out).  res_in may alias out.
-int gemm_res(const Ctx& c, const bf16* A, int lda, const bf16* W, const float* bias, int M, int N, int K,
-             const bf16* res_in, bf16* out, float* st_out, const bf16* A2 = nullptr, int lda2 = 0, int K1 = 0) {
-  pdm::GemmArgs a{};
-  a.A1 = A; a.lda1 = lda;
-  a.A2 = A2; a.lda2 = lda2;
-  a.K1 = A2 ? K1 : K;
-  a.W = W; a.bias = bias;
+  a.ln_stats = st_in; a.ln_ld = T; a.ln_D = K; a.ln_eps = 1e-5f; a.ln_colsum = lw.colsum; a.stats_ld = T;
+  a.A1 = A; a.lda1 = K; a.K1 = K;
+  a.W = lw.w; a.bias = lw.bias;
   a.M = M; a.N = N; a.K = K;
   a.out_bf16 = out; a.ldo = N;
-  a.res_in = res_in; a.ldri = N; a.accumulate = res_in ? 1 : 0;
-  a.stats_out = st_out; a.stats_ld = (N + 255) / 256;
-  return launch_gemm(c, a, pdm::EPI_RES);
+  return a;
 }
 
-// One U-ViT Block on the bf16 residual stream (the reference under bf16 autocast keeps x in the autocast dtype:
-// each Linear's output is added to x in that dtype).  xin = the block input x (bf16) with partials st_in; the
-// block output goes to xout (may equal xin only when xin is not needed afterwards) with partials st_out.  The
-// block-internal x lives in XT.  Per residual GEMM the epilogue moves 2 + 2 bytes per element instead of the
-// fp32 stream's 4 + 4 + a 2-byte bf16 operand copy.
-int run_block16(const Ctx& c, const std::string& pre, int nseq, int L, const bf16* xin, const float* st_in,
-                const bf16* skip_in, bf16* xout, float* st_out, const Workspace& w) {
+// GemmArgs of a residual-producing Linear (skip_linear, proj, fc2, the t2i injection): D output columns and their
+// LayerNorm partials in st_out.  With A2, the second split-K operand, it is skip_linear(cat([x, skip], -1)), whose
+// output replaces x; every other one adds to x.
+//   bf16 stream (EPI_RES): out = bf16(A W^T + bias (+ res)); res may alias out
+//   fp32 stream (EPI_F32): X (+)= A W^T + bias, and out (may be null) takes bf16 of the new X
+pdm::GemmArgs res_lin(const pdm_uvit* h, Mode m, const bf16* A, int lda, const bf16* A2, const LinW& lw, int M, int K,
+                      float* X, const bf16* res, bf16* out, float* st_out) {
+  pdm::GemmArgs a{};
+  const int D = h->D, T = (D + 255) / 256;
+  a.A1 = A; a.lda1 = lda;
+  a.A2 = A2; a.lda2 = A2 ? D : 0;
+  a.K1 = A2 ? D : K;
+  a.W = lw.w; a.bias = lw.bias;
+  a.M = M; a.N = D; a.K = K;
+  a.out_bf16 = out; a.ldo = D;
+  a.accumulate = A2 ? 0 : 1;
+  a.stats_out = st_out; a.stats_ld = T;
+  if (m.r16) {
+    a.res_in = res; a.ldri = D;
+  } else {
+    a.out_f32 = X; a.ldr = D;
+    // the bf16 Linears of the fp32 stream have always carried these, though none consumes a LayerNorm
+    if (!m.f8) { a.ln_ld = T; a.ln_D = K; a.ln_eps = 1e-5f; }
+  }
+  return a;
+}
+
+// MXFP8 decoration of a built block Linear (an MXFP8 net, Mode::f8).  A8: the MXFP8 A operand in place of the bf16
+// one, on the block-scaled MFMA against the e4m3 weight + its "_scale"; a LayerNorm consumer then takes A
+// group-centred (GemmArgs::ln_gcol).  A8 null: a bf16 Linear (skip_linear, a bf16 fc1).  out8.q set: the epilogue
+// also writes the MXFP8 copy of what it stores, the next Linear's operand, group-centred when written beside
+// LayerNorm partials (GemmArgs::mx_center).
+void mx_decorate(const pdm_uvit* h, pdm::GemmArgs& a, const Q8* A8, const LinW& lw, const Q8& out8) {
+  if (A8) {
+    a.A1 = (const bf16*)A8->q; a.lda1 = A8->ld;
+    a.fp8 = 1;
+    a.a_scale = A8->s; a.a_scale_ld = A8->sld;
+    a.w_scale = lw.scale; a.w_scale_ld = a.N;
+    if (a.ln_stats) a.ln_gcol = lw.gcol;
+    a.ln_ld = (h->D + 255) / 256; a.ln_D = a.K; a.ln_eps = 1e-5f;
+  }
+  a.out_fp8 = out8.q; a.ldo8 = out8.ld; a.out_scale = out8.s; a.out_scale_ld = out8.sld;
+  a.mx_center = out8.q && a.stats_out ? 1 : 0;
+  // an MXFP8 net's launches have always carried the leading dimensions of their present outputs only
+  a.ldo = a.out_bf16 ? a.N : 0;
+  a.ldr = a.out_f32 ? h->D : 0;
+  a.ldri = a.res_in ? a.N : 0;
+}
+
+// One stream of a block: weights, rows, where x comes from and goes to, and the block's scratch
+struct BlockIO {
+  const BlockW* W;
+  int L;                 // tokens per sequence
+  float* X;              // fp32 stream: the residual rows [rows L, D], updated in place; null on the bf16 stream
+  const bf16* xin;       // the block input: x itself (bf16 stream) or its bf16 copy (fp32 stream)
+  const float* st_in;    // LayerNorm partials of the input
+  const bf16* skip_in;   // long-skip activation [rows L, D] (out-blocks), or null
+  bf16* xout;            // where fc2 leaves the block output in bf16 (fp32 stream: may be null)
+  float* st_out;         // and its partials (fp32 stream: may be null)
+  bf16 *XT, *QKV, *ATT, *MLP;   // scratch: the block-internal x (bf16), qkv, attention output, GELU(fc1)
+  float* STT;                   // partials of the block-internal x
+  Q8 in8, out8;          // MXFP8 net: the input as the qkv operand; where fc2 leaves the output for the next qkv
+};
+
+// One U-ViT Block (libs/uvit.py:115-120) for n = 1 or 2 streams in lockstep, norm1 / norm2 fused into qkv / fc1:
+//   [x = skip_linear(cat([x, skip]))]  qkv = norm1(x) W^T  attention  x += proj(attn)  h = GELU(fc1(norm2(x)))
+//   x += fc2(h)
+// Each producing epilogue (skip_linear, proj, fc2) leaves x and its LayerNorm partials in the form its consumer
+// reads.  Two streams (the mask and the image block of a t2i layer: same D / Hid, different weights, rows and
+// buffers) share every Linear as one grouped launch; attention runs per stream.  In an MXFP8 net (one stream) the
+// Linears' operands are the workspace's MXFP8 buffers: xtq the block-internal x, atq the attention output, mlq
+// GELU(fc1), which is then stored only so.  skip_linear stays bf16 there: its output REPLACES the residual stream,
+// and in MXFP8 it alone costs 6.3e-2 rel-L2 of the H/4 forward for 7 % of the FLOPs; attention stays
+// bf16 too (a 72-deep QK^T cannot fill the 128-deep scaled MFMA).
+int run_block(const Ctx& c, Mode m, int nseq, int n, const BlockIO* io, const Workspace& w) {
   const pdm_uvit* h = c.h;
-  const int D = h->D, M = nseq * L;
-  const bf16* x = xin;
-  const float* st = st_in;
-  if (skip_in) {  // x = skip_linear(cat([x, skip], -1)): split-K over the two bf16 operands
-    PDM_TRY(gemm_res(c, xin, D, h->w(pre + ".skip_linear.weight"), h->f(pre + ".skip_linear.bias"), M, D, 2 * D,
-                     nullptr, w.XT, w.STT, skip_in, D, D));
-    x = w.XT;
-    st = w.STT;
+  const int D = h->D, Hid = h->Hid;
+  const bool f8 = m.f8 != 0, fc1_8 = (m.f8 & 4) != 0;
+  const int res_epi = m.r16 ? pdm::EPI_RES : pdm::EPI_F32;
+  if (n == 2 && (f8 || !io[0].skip_in != !io[1].skip_in))
+    return fail(PDM_ERR_STATE, "run_block: paired streams are bf16 Linears with long skips in both or neither");
+  pdm::GemmArgs g[2];
+  auto launch = [&](int epi) { return n == 2 ? launch_gemm_pair(c, g[0], g[1], epi) : launch_gemm(c, g[0], epi); };
+  // XT as the bf16 operand of block Linear `bit`: the bf16 stream's x is there anyway; the fp32 stream stores the
+  // copy only for a bf16 consumer
+  auto xt = [&](const BlockIO& s, int bit) { return m.r16 || !((m.f8 >> bit) & 1) ? s.XT : nullptr; };
+  const bf16* x[2] = {io[0].xin, n == 2 ? io[1].xin : nullptr};
+  const float* st[2] = {io[0].st_in, n == 2 ? io[1].st_in : nullptr};
+  Q8 x8 = io[0].in8;
+  if (io[0].skip_in) {  // x = skip_linear(cat([x, skip], -1)): split-K over the two bf16 operands
+    for (int i = 0; i < n; ++i) {
+      const BlockIO& s = io[i];
+      g[i] = res_lin(h, m, s.xin, D, s.skip_in, s.W->skip, nseq * s.L, 2 * D, s.X, nullptr, xt(s, 0), s.STT);
+      if (f8) mx_decorate(h, g[i], nullptr, s.W->skip, w.xtq);
+      x[i] = s.XT;
+      st[i] = s.STT;
+    }
+    PDM_TRY(launch(res_epi));
+    x8 = w.xtq;
   }
-  {  // qkv = norm1(x) W^T
-    LnIO io;
-    io.st_in = st;
-    io.colsum = h->f(pre + ".attn.qkv.ln_colsum");
-    PDM_TRY(gemm(c, x, D, h->w(pre + ".attn.qkv.weight"), h->f(pre + ".attn.qkv.ln_bias"), M, 3 * D, D,
-                 pdm::EPI_BF16, w.QKV, 3 * D, nullptr, 0, 0, nullptr, 0, 0, 0, 0, io));
+  for (int i = 0; i < n; ++i) {  // qkv = norm1(x) W^T (bf16 for the attention kernel)
+    const BlockIO& s = io[i];
+    g[i] = ln_lin(h, x[i], s.W->qkv, nseq * s.L, 3 * D, D, s.QKV, st[i]);
+    if (f8) mx_decorate(h, g[i], &x8, s.W->qkv, Q8());
   }
-  {
+  PDM_TRY(launch(pdm::EPI_BF16));
+  for (int i = 0; i < n; ++i) {
+    const BlockIO& s = io[i];
     pdm::AttentionArgs a{};
-    a.qkv = w.QKV; a.ldq = 3 * D;
-    a.out = w.ATT; a.ldo = D;
-    a.B = nseq; a.L = L; a.H = h->H; a.Dh = h->Dh;
+    a.qkv = s.QKV; a.ldq = 3 * D;
+    a.out = s.ATT; a.ldo = D;
+    a.B = nseq; a.L = s.L; a.H = h->H; a.Dh = h->Dh;
     a.scale = 1.0f / sqrtf((float)h->Dh);
     a.q_log2 = 1;   // attn.qkv's q rows are packed pre-scaled by Dh^-0.5 log2(e) (include/pdm.h)
     PDM_CHECK(pdm::attention_check(a));
     PDM_HIP(pdm::attention_launch(a, c.s));
+    if (f8) PDM_HIP(pdm::mxq_launch(s.ATT, 1, D, nseq * s.L, D, w.atq.q, w.atq.ld, w.atq.s, w.atq.sld, c.s));
   }
-  // x += proj(attn) -> XT (in place when x already is XT; xin itself may be a long-skip operand kept for later)
-  PDM_TRY(gemm_res(c, w.ATT, D, h->w(pre + ".attn.proj.weight"), h->f(pre + ".attn.proj.bias"), M, D, D, x, w.XT,
-                   w.STT));
-  {  // h = GELU(fc1(norm2(x)))
-    LnIO io;
-    io.st_in = w.STT;
-    io.colsum = h->f(pre + ".mlp.fc1.ln_colsum");
-    PDM_TRY(gemm(c, w.XT, D, h->w(pre + ".mlp.fc1.weight"), h->f(pre + ".mlp.fc1.ln_bias"), M, h->Hid, D,
-                 pdm::EPI_GELU, w.MLP, h->Hid, nullptr, 0, 0, nullptr, 0, 0, 0, 0, io));
+  for (int i = 0; i < n; ++i) {  // x += proj(attn) -> X / XT (xin itself may be a long-skip operand kept for later)
+    const BlockIO& s = io[i];
+    g[i] = res_lin(h, m, s.ATT, D, nullptr, s.W->proj, nseq * s.L, D, s.X, x[i], xt(s, 2), s.STT);
+    if (f8) mx_decorate(h, g[i], &w.atq, s.W->proj, fc1_8 ? w.xtq : Q8());
   }
-  // x += fc2(h) -> xout
-  PDM_TRY(gemm_res(c, w.MLP, h->Hid, h->w(pre + ".mlp.fc2.weight"), h->f(pre + ".mlp.fc2.bias"), M, D, h->Hid, w.XT,
-                   xout, st_out));
-  return PDM_OK;
+  PDM_TRY(launch(res_epi));
+  for (int i = 0; i < n; ++i) {  // h = GELU(fc1(norm2(x)))
+    const BlockIO& s = io[i];
+    g[i] = ln_lin(h, s.XT, s.W->fc1, nseq * s.L, Hid, D, f8 ? nullptr : s.MLP, s.STT);
+    if (f8) mx_decorate(h, g[i], fc1_8 ? &w.xtq : nullptr, s.W->fc1, w.mlq);
+    if (f8 && !fc1_8) g[i].stats_ld = 0;   // (the bf16 fc1 of an MXFP8 net has always carried 0 here)
+  }
+  PDM_TRY(launch(pdm::EPI_GELU));
+  for (int i = 0; i < n; ++i) {  // x += fc2(h) -> X / xout
+    const BlockIO& s = io[i];
+    g[i] = res_lin(h, m, s.MLP, Hid, nullptr, s.W->fc2, nseq * s.L, Hid, s.X, s.XT, s.xout, s.st_out);
+    if (f8) mx_decorate(h, g[i], &w.mlq, s.W->fc2, s.out8);
+  }
+  return launch(res_epi);
 }
 
-// One block of each t2i stream in lockstep on the bf16 residual stream (run_block16's sequence): every Linear of the
-// two blocks (same D / Hid, different weights, rows and buffers) is one grouped launch, attention runs per stream.
-// The t2i layer's image (L = 334) and mask (L = 590) blocks are independent given x, and each alone launches under
-// one wave of 256-row tiles at the bench's rows (t2i B = 32 per GPU as two lanes: 84 / 148 tiles for N = 512).
-struct BlockIO {
-  std::string pre;
-  int L;
-  const bf16* xin;
-  const float* st_in;
-  const bf16* skip_in;
-  bf16* xout;
-  float* st_out;
-  bf16 *XT, *QKV, *ATT, *MLP;
-  float* STT;
-};
-int run_block16_pair(const Ctx& c, int nseq, const BlockIO& A, const BlockIO& B) {
-  const pdm_uvit* h = c.h;
-  const int D = h->D;
-  const int Ma = nseq * A.L, Mb = nseq * B.L;
-  const bf16* xa = A.xin;
-  const bf16* xb = B.xin;
-  const float* sa = A.st_in;
-  const float* sb = B.st_in;
-  if (A.skip_in || B.skip_in) {   // x = skip_linear(cat([x, skip], -1)); both streams have long skips or neither
-    if (!A.skip_in || !B.skip_in) return fail(PDM_ERR_STATE, "run_block16_pair: long skip in one stream only");
-    PDM_TRY(launch_gemm_pair(c,
-        res_args(A.xin, D, h->w(A.pre + ".skip_linear.weight"), h->f(A.pre + ".skip_linear.bias"), Ma, D, 2 * D, nullptr,
-                 A.XT, A.STT, A.skip_in, D, D),
-        res_args(B.xin, D, h->w(B.pre + ".skip_linear.weight"), h->f(B.pre + ".skip_linear.bias"), Mb, D, 2 * D, nullptr,
-                 B.XT, B.STT, B.skip_in, D, D),
-        pdm::EPI_RES));
-    xa = A.XT; sa = A.STT;
-    xb = B.XT; sb = B.STT;
-  }
-  PDM_TRY(launch_gemm_pair(c,   // qkv = norm1(x) W^T
-      ln_args(h, xa, h->w(A.pre + ".attn.qkv.weight"), h->f(A.pre + ".attn.qkv.ln_bias"), Ma, 3 * D, D, A.QKV, sa,
-              h->f(A.pre + ".attn.qkv.ln_colsum")),
-      ln_args(h, xb, h->w(B.pre + ".attn.qkv.weight"), h->f(B.pre + ".attn.qkv.ln_bias"), Mb, 3 * D, D, B.QKV, sb,
-              h->f(B.pre + ".attn.qkv.ln_colsum")),
-      pdm::EPI_BF16));
-  for (const BlockIO* io : {&A, &B}) {
-    pdm::AttentionArgs a{};
-    a.qkv = io->QKV; a.ldq = 3 * D;
-    a.out = io->ATT; a.ldo = D;
-    a.B = nseq; a.L = io->L; a.H = h->H; a.Dh = h->Dh;
-    a.scale = 1.0f / sqrtf((float)h->Dh);
-    a.q_log2 = 1;
-    PDM_CHECK(pdm::attention_check(a));
-    PDM_HIP(pdm::attention_launch(a, c.s));
-  }
-  PDM_TRY(launch_gemm_pair(c,   // x += proj(attn) -> XT
-      res_args(A.ATT, D, h->w(A.pre + ".attn.proj.weight"), h->f(A.pre + ".attn.proj.bias"), Ma, D, D, xa, A.XT, A.STT),
-      res_args(B.ATT, D, h->w(B.pre + ".attn.proj.weight"), h->f(B.pre + ".attn.proj.bias"), Mb, D, D, xb, B.XT, B.STT),
-      pdm::EPI_RES));
-  PDM_TRY(launch_gemm_pair(c,   // h = GELU(fc1(norm2(x)))
-      ln_args(h, A.XT, h->w(A.pre + ".mlp.fc1.weight"), h->f(A.pre + ".mlp.fc1.ln_bias"), Ma, h->Hid, D, A.MLP, A.STT,
-              h->f(A.pre + ".mlp.fc1.ln_colsum")),
-      ln_args(h, B.XT, h->w(B.pre + ".mlp.fc1.weight"), h->f(B.pre + ".mlp.fc1.ln_bias"), Mb, h->Hid, D, B.MLP, B.STT,
-              h->f(B.pre + ".mlp.fc1.ln_colsum")),
-      pdm::EPI_GELU));
-  PDM_TRY(launch_gemm_pair(c,   // x += fc2(h) -> xout
-      res_args(A.MLP, h->Hid, h->w(A.pre + ".mlp.fc2.weight"), h->f(A.pre + ".mlp.fc2.bias"), Ma, D, h->Hid, A.XT, A.xout,
-               A.st_out),
-      res_args(B.MLP, h->Hid, h->w(B.pre + ".mlp.fc2.weight"), h->f(B.pre + ".mlp.fc2.bias"), Mb, D, h->Hid, B.XT, B.xout,
-               B.st_out),
-      pdm::EPI_RES));
-  return PDM_OK;
+// a block stream on the workspace's first scratch set
+BlockIO block_io(const Workspace& w, const BlockW& W, int L) {
+  BlockIO s{};
+  s.W = &W; s.L = L;
+  s.XT = w.XT; s.QKV = w.QKV; s.ATT = w.ATT; s.MLP = w.MLP; s.STT = w.STT;
+  return s;
 }
 
 // bf16 copy + LayerNorm partials of fp32 rows no GEMM epilogue produced (token assembly, mask-stream refresh)
@@ -624,203 +594,113 @@ int row_stats(const Ctx& c, const float* X, int rows, bf16* xb, float* st) {
   return PDM_OK;
 }
 
-// The single-stream block stack (libs/uvit.py:213-222, libs/uvit_t2i.py:407-410 / 516): X holds the assembled
-// tokens; in-block i leaves bf16 of its output in SK[i] (the long-skip operand and the next block's A operand).
-int run_stack(const Ctx& c, const Workspace& w, int rows, int L) {
+// The single-stream block stack (libs/uvit.py:213-222, libs/uvit_t2i.py:407-410 / 516) over the assembled fp32
+// tokens X.  Every activation is produced once, by the epilogue that computes it, in the precision and layout of
+// its consumers; what a block leaves for the next one, in every mode:
+//   * the LayerNorm partials of its output, in ST;
+//   * its output in bf16 -- x itself on the bf16 stream, else the copy a bf16 qkv, a skip_linear or a long skip
+//     reads: an in-block's in SK[i], the long-skip slot (with bf16 Linears always: it is also the next block's
+//     operand; in an MXFP8 net only if the net has long skips), every other block's in XB.  The fp32 stream of an
+//     MXFP8 net without long skips has no bf16 reader, and none is stored;
+//   * in an MXFP8 net also its output as MXFP8 in xq, the next qkv operand, unless the next block starts with
+//     skip_linear (bf16 operands).
+// A block reads its input before its fc2 writes the output, so XB is updated in place.  The last out-block of the
+// fp32 stream leaves nothing but X (the final norm reads it); on the bf16 stream XB is the result.
+int run_stack(const Ctx& c, Mode m, const Workspace& w, int rows, int L) {
   const pdm_uvit* h = c.h;
-  const size_t MD = (size_t)rows * L * h->D;
-  PDM_TRY(row_stats(c, w.X, rows * L, w.XB, w.ST));
-  const bf16* xb = w.XB;
-  for (int i = 0; i < h->nhalf; ++i) {
-    PDM_TRY(run_block(c, "in_blocks." + std::to_string(i), w.X, rows, L, xb, w.ST, nullptr, w.SK + i * MD, w.ST, w));
-    xb = w.SK + i * MD;
-  }
-  PDM_TRY(run_block(c, "mid_block", w.X, rows, L, xb, w.ST, nullptr, w.XB, w.ST, w));
-  for (int i = 0; i < h->nhalf; ++i) {
-    const bf16* sk = h->cfg.skip ? w.SK + (h->nhalf - 1 - i) * MD : nullptr;
-    const bool last = i + 1 == h->nhalf;
-    PDM_TRY(run_block(c, "out_blocks." + std::to_string(i), w.X, rows, L, w.XB, w.ST, sk, last ? nullptr : w.XB,
-                      last ? nullptr : w.ST, w));
-  }
-  return PDM_OK;
-}
-
-// The block stack on the bf16 residual stream: the assembled fp32 tokens X become bf16 XB (+ partials); in-block
-// i leaves its output in SK[i] (the long skip and the next block's input); mid / out-blocks update XB.
-int run_stack16(const Ctx& c, const Workspace& w, int rows, int L) {
-  const pdm_uvit* h = c.h;
-  const size_t MD = (size_t)rows * L * h->D;
-  PDM_TRY(row_stats(c, w.X, rows * L, w.XB, w.ST));
-  const bf16* x = w.XB;
-  for (int i = 0; i < h->nhalf; ++i) {
-    PDM_TRY(run_block16(c, "in_blocks." + std::to_string(i), rows, L, x, w.ST, nullptr, w.SK + i * MD, w.ST, w));
-    x = w.SK + i * MD;
-  }
-  PDM_TRY(run_block16(c, "mid_block", rows, L, x, w.ST, nullptr, w.XB, w.ST, w));
-  for (int i = 0; i < h->nhalf; ++i) {
-    const bf16* sk = h->cfg.skip ? w.SK + (h->nhalf - 1 - i) * MD : nullptr;
-    PDM_TRY(run_block16(c, "out_blocks." + std::to_string(i), rows, L, w.XB, w.ST, sk, w.XB, w.ST, w));
-  }
-  return PDM_OK;
-}
-
-// One U-ViT Block with MXFP8 qkv / proj / fc1 / fc2 (cfg.fp8, BASELINE configs[4]).  `in` is the MXFP8 block
-// input x with LayerNorm partials st_in.  Out-blocks with a long skip start from skip_linear(cat([x, skip]))
-// (libs/uvit.py:116-117) instead, kept in bf16 on the split-K GEMM over xb_in / skip_in: its output REPLACES the
-// residual stream, and in MXFP8 it alone costs 6.3e-2 rel-L2 of the H/4 forward (vs 1.6-4.4e-2 for each of the
-// other Linears; fp32 fake-quant of the oracle) for 7 % of the FLOPs.  Attention stays bf16 (a
-// 72-deep QK^T cannot fill the 128-deep scaled MFMA, and the unscaled fp8 MFMA runs at the bf16 rate); its output
-// is MX-quantised for proj.  fc2 leaves the block output as MXFP8 in out8 and / or bf16 in outb (either may be
-// null) and its partials in st_out.
-//
-// X == nullptr: the bf16 residual stream (cfg.residual_fp32 == 0): xb_in is the block input x itself (bf16), the
-// residual epilogues are EPI_RES, the block-internal x lives in XT and the block output goes to outb (required).
-int run_block8(const Ctx& c, const std::string& pre, float* X, int M, int L, const Q8& in, const float* st_in,
-               const bf16* xb_in, const bf16* skip_in, const Q8& out8, bf16* outb, float* st_out, const Workspace& w) {
-  const pdm_uvit* h = c.h;
-  const int D = h->D;
-  const bool r16 = X == nullptr;
-  Q8 a = in;
-  const float* st = st_in;
-  const bf16* res = xb_in;   // (r16) the residual x the block adds to
-  if (skip_in) {  // x = skip_linear(cat([x, skip], -1)) -> X (fp32) / XT (bf16) + its MXFP8 copy (qkv operand) + partials
-    pdm::GemmArgs g{};
-    g.A1 = xb_in; g.lda1 = D; g.A2 = skip_in; g.lda2 = D; g.K1 = D;
-    g.W = h->w(pre + ".skip_linear.weight"); g.bias = h->f(pre + ".skip_linear.bias");
-    g.M = M; g.N = D; g.K = 2 * D;
-    if (r16) { g.out_bf16 = w.XT; g.ldo = D; }
-    else { g.out_f32 = X; g.ldr = D; }
-    g.stats_out = w.STT; g.stats_ld = (D + 255) / 256;
-    g.out_fp8 = w.xtq.q; g.ldo8 = w.xtq.ld; g.out_scale = w.xtq.s; g.out_scale_ld = w.xtq.sld;
-    g.mx_center = 1;
-    PDM_TRY(launch_gemm(c, g, r16 ? pdm::EPI_RES : pdm::EPI_F32));
-    a = w.xtq;
-    st = w.STT;
-    res = w.XT;
-  }
-  {  // qkv = norm1(x) W^T (bf16 for the attention kernel)
-    LnIO io;
-    io.st_in = st;
-    io.colsum = h->f(pre + ".attn.qkv.ln_colsum");
-    PDM_TRY(gemm8(c, a, pre + ".attn.qkv.weight", h->f(pre + ".attn.qkv.ln_bias"), M, 3 * D, D, pdm::EPI_BF16, w.QKV,
-                  nullptr, 0, io, Q8()));
-  }
-  {
-    pdm::AttentionArgs at{};
-    at.qkv = w.QKV; at.ldq = 3 * D;
-    at.out = w.ATT; at.ldo = D;
-    at.B = M / L; at.L = L; at.H = h->H; at.Dh = h->Dh;
-    at.scale = 1.0f / sqrtf((float)h->Dh);
-    at.q_log2 = 1;
-    PDM_CHECK(pdm::attention_check(at));
-    PDM_HIP(pdm::attention_launch(at, c.s));
-    PDM_HIP(pdm::mxq_launch(w.ATT, 1, D, M, D, w.atq.q, w.atq.ld, w.atq.s, w.atq.sld, c.s));
-  }
-  const bool fc1_8 = h->f8(2);
-  {  // x += proj(attn) -> X / XT, its partials and the fc1 operand (centred MXFP8, or bf16 for a bf16 fc1)
-    LnIO io;
-    io.st_out = w.STT;
-    if (r16)
-      PDM_TRY(gemm8(c, w.atq, pre + ".attn.proj.weight", h->f(pre + ".attn.proj.bias"), M, D, D, pdm::EPI_RES, w.XT,
-                    nullptr, 1, io, fc1_8 ? w.xtq : Q8(), res));
-    else
-      PDM_TRY(gemm8(c, w.atq, pre + ".attn.proj.weight", h->f(pre + ".attn.proj.bias"), M, D, D, pdm::EPI_F32,
-                    fc1_8 ? nullptr : w.XT, X, 1, io, fc1_8 ? w.xtq : Q8()));
-  }
-  {  // h = GELU(fc1(norm2(x))), stored only as the MXFP8 fc2 operand
-    LnIO io;
-    io.st_in = w.STT;
-    io.colsum = h->f(pre + ".mlp.fc1.ln_colsum");
-    if (fc1_8) {
-      PDM_TRY(gemm8(c, w.xtq, pre + ".mlp.fc1.weight", h->f(pre + ".mlp.fc1.ln_bias"), M, h->Hid, D, pdm::EPI_GELU,
-                    nullptr, nullptr, 0, io, w.mlq));
-    } else {   // bf16 MFMA, fused LayerNorm on the bf16 copy, GELU epilogue emitting the MXFP8 fc2 operand only
-      pdm::GemmArgs g{};
-      const int T = (D + 255) / 256;
-      g.A1 = w.XT; g.lda1 = D; g.K1 = D;
-      g.W = h->w(pre + ".mlp.fc1.weight"); g.bias = h->f(pre + ".mlp.fc1.ln_bias");
-      g.M = M; g.N = h->Hid; g.K = D;
-      g.ln_stats = w.STT; g.ln_ld = T; g.ln_D = D; g.ln_eps = 1e-5f; g.ln_colsum = io.colsum;
-      g.out_fp8 = w.mlq.q; g.ldo8 = w.mlq.ld; g.out_scale = w.mlq.s; g.out_scale_ld = w.mlq.sld;
-      PDM_TRY(launch_gemm(c, g, pdm::EPI_GELU));
-    }
-  }
-  {  // x += fc2(h)
-    LnIO io;
-    io.st_out = st_out;
-    if (r16)
-      PDM_TRY(gemm8(c, w.mlq, pre + ".mlp.fc2.weight", h->f(pre + ".mlp.fc2.bias"), M, D, h->Hid, pdm::EPI_RES, outb,
-                    nullptr, 1, io, out8, w.XT));
-    else
-      PDM_TRY(gemm8(c, w.mlq, pre + ".mlp.fc2.weight", h->f(pre + ".mlp.fc2.bias"), M, D, h->Hid, pdm::EPI_F32, outb,
-                    X, 1, io, out8));
-  }
-  return PDM_OK;
-}
-
-// run_stack8 on the bf16 residual stream: in-block i leaves x in SK[i] (bf16: the long skip and the next block's
-// residual) and MXFP8 xq (the next qkv operand); the mid / out-blocks update XB.
-int run_stack8_16(const Ctx& c, const Workspace& w, int rows, int L) {
-  const pdm_uvit* h = c.h;
-  const int D = h->D, M = rows * L, n = h->nhalf;
-  const bool skip = h->cfg.skip != 0;
+  const int D = h->D, M = rows * L;
   const size_t MD = (size_t)M * D;
-  PDM_HIP(pdm::rowstats_launch(w.X, D, M, D, w.XB, D, w.ST, (D + 255) / 256, c.s, w.xq.q, w.xq.ld, w.xq.s,
-                               w.xq.sld, 1));
-  // a block reads its input x (skip_linear or proj) before fc2 writes the output, so XB can be updated in place;
-  // in-block outputs with long skips are kept in SK[i]
+  const bool f8 = m.f8 != 0, skip = h->cfg.skip != 0;
+  const bool no_bf16 = f8 && !m.r16 && !skip;
+  bf16* xb0 = f8 && !m.r16 ? nullptr : w.XB;   // (MXFP8 net, fp32 stream: the first qkv reads xq)
+  PDM_HIP(pdm::rowstats_launch(w.X, D, M, D, xb0, xb0 ? D : 0, w.ST, (D + 255) / 256, c.s, w.xq.q, w.xq.ld, w.xq.s,
+                               w.xq.sld, f8 ? 1 : 0));
   const bf16* x = w.XB;
-  for (int i = 0; i < n; ++i) {
-    bf16* o = skip ? w.SK + i * MD : w.XB;
-    PDM_TRY(run_block8(c, "in_blocks." + std::to_string(i), nullptr, M, L, w.xq, w.ST, x, nullptr, w.xq, o, w.ST, w));
-    x = o;
-  }
-  PDM_TRY(run_block8(c, "mid_block", nullptr, M, L, w.xq, w.ST, x, nullptr, skip ? Q8() : w.xq, w.XB, w.ST, w));
-  for (int i = 0; i < n; ++i)
-    PDM_TRY(run_block8(c, "out_blocks." + std::to_string(i), nullptr, M, L, w.xq, w.ST, w.XB,
-                       skip ? w.SK + (n - 1 - i) * MD : nullptr, skip ? Q8() : w.xq, w.XB, w.ST, w));
-  return PDM_OK;
-}
-
-// The block stack with MXFP8 block Linears: in-blocks leave their output as MXFP8 (the next block's operand) and
-// as bf16 in SK[i] (the long skip); the mid block and out-blocks leave bf16 x in XB for the next skip_linear (or,
-// without long skips, MXFP8 x for the next qkv).  Every activation is produced once, by the epilogue that computes
-// it, in the precision and layout of its consumer.
-int run_stack8(const Ctx& c, const Workspace& w, int rows, int L) {
-  const pdm_uvit* h = c.h;
-  const int D = h->D, M = rows * L, n = h->nhalf;
-  const bool skip = h->cfg.skip != 0;
-  const size_t MD = (size_t)M * D;
-  PDM_HIP(pdm::rowstats_launch(w.X, D, M, D, nullptr, 0, w.ST, (D + 255) / 256, c.s, w.xq.q, w.xq.ld, w.xq.s,
-                               w.xq.sld, 1));
-  for (int i = 0; i < n; ++i)
-    PDM_TRY(run_block8(c, "in_blocks." + std::to_string(i), w.X, M, L, w.xq, w.ST, nullptr, nullptr, w.xq,
-                       skip ? w.SK + i * MD : nullptr, w.ST, w));
-  PDM_TRY(run_block8(c, "mid_block", w.X, M, L, w.xq, w.ST, nullptr, nullptr, skip ? Q8() : w.xq,
-                     skip ? w.XB : nullptr, w.ST, w));
-  for (int i = 0; i < n; ++i) {
-    const bool last = i + 1 == n;
-    PDM_TRY(run_block8(c, "out_blocks." + std::to_string(i), w.X, M, L, w.xq, w.ST, w.XB,
-                       skip ? w.SK + (n - 1 - i) * MD : nullptr, last || skip ? Q8() : w.xq,
-                       last || !skip ? nullptr : w.XB, last ? nullptr : w.ST, w));
+  for (const Layer& ly : h->layers) {
+    const bool last = ly.last && !m.r16;
+    BlockIO s = block_io(w, ly.img, L);
+    s.X = m.r16 ? nullptr : w.X;
+    s.xin = x; s.st_in = w.ST;
+    s.skip_in = ly.skip_from >= 0 ? w.SK + ly.skip_from * MD : nullptr;
+    s.xout = ly.keep >= 0 && (skip || !f8) ? w.SK + ly.keep * MD : last || no_bf16 ? nullptr : w.XB;
+    s.st_out = last ? nullptr : w.ST;
+    s.in8 = w.xq;
+    if (f8 && !last && (ly.keep >= 0 || !skip)) s.out8 = w.xq;
+    PDM_TRY(run_block(c, m, rows, 1, &s, w));
+    x = s.xout;
   }
   return PDM_OK;
 }
 
+// every weight registered; the resolved table follows the registrations (pdm_uvit_set_param marks it dirty)
 int check_ready(pdm_uvit* h) {
+  if (!h->dirty) return PDM_OK;
   for (auto& n : h->order)
     if (!h->params[n].ptr) return fail(PDM_ERR_STATE, "pdm_uvit: weight not registered: " + n);
+  h->resolve();
+  return PDM_OK;
+}
+
+// What both forward entry points do before the first launch: the weights resolved, the workspace laid out and
+// checked, the profiling hook rewound, the forward's stream-K state
+int begin_forward(pdm_uvit* h, const char* who, int rows, void* workspace, size_t workspace_bytes, void* stream,
+                  Workspace& w, Ctx& c) {
+  PDM_TRY(check_ready(h));
+  w = layout(h, rows, (char*)workspace);
+  if (w.bytes > workspace_bytes) return fail(PDM_ERR_ARG, std::string(who) + ": workspace too small");
+  h->prof_n = 0;
+  c.h = h;
+  c.s = (hipStream_t)stream;
+  return sk_begin(c, &c.sk_used);
+}
+
+// The image stream's tokens [label?, time, context x n_ctx?, patches] + pos_embed -> the first Lx rows of each
+// L_total-row sequence of X (libs/uvit.py:205-211: [label, time, patches]; libs/uvit_t2i.py:401-405 / 408-409:
+// [time, context, patches]); only pos_embed rows [0, Lx) are read
+int assemble_image(const Ctx& c, const Workspace& w, const float* x, const float* t, const int64_t* y, int rows,
+                   int L_total) {
+  const pdm_uvit* h = c.h;
+  const bool t2i = h->cfg.t2i != 0;
+  pdm::AssembleArgs a{};
+  a.img = x; a.C = h->C; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
+  a.patch_w = h->patch_w; a.patch_b = h->patch_b;
+  a.t = t; a.y = y;
+  a.label_emb = h->label_emb;
+  if (t2i) { a.ctx_tokens = w.CTXF; a.n_ctx = h->cfg.num_clip_token; }
+  a.pos = h->pos;
+  a.out = w.X; a.ld_out = h->D;
+  a.B = rows; a.D = h->D; a.L_total = L_total;
+  a.row0_patch = h->extras;
+  a.time_row = t2i ? 0 : h->extras - 1;
+  a.label_row = y ? 0 : -1;
+  a.ctx_row = t2i ? 1 : -1;
+  PDM_CHECK(pdm::assemble_check(a));
+  PDM_HIP(pdm::assemble_launch(a, c.s));
+  return PDM_OK;
+}
+
+// The mask patches mask_embed(mask_token) + pos -> rows [Lx, Lm) of each Lm-row sequence that starts at `out`
+int assemble_mask(const Ctx& c, const float* mask_token, const float* pos, float* out, int rows) {
+  const pdm_uvit* h = c.h;
+  pdm::AssembleArgs a{};
+  a.img = mask_token; a.C = h->K; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
+  a.patch_w = h->mask_w; a.patch_b = h->mask_b;
+  a.pos = pos;
+  a.out = out + (size_t)h->Lx * h->D; a.ld_out = h->D; a.B = rows; a.D = h->D; a.L_total = h->Lm;
+  a.row0_patch = 0; a.time_row = -1; a.label_row = -1; a.ctx_row = -1;
+  PDM_CHECK(pdm::assemble_check(a));
+  PDM_HIP(pdm::assemble_launch(a, c.s));
   return PDM_OK;
 }
 
 // decoder_pred-style head on bf16 token rows: token (b, i) is row b * group_stride + row_offset + i of `hin`.
-int run_head(const Ctx& c, const bf16* hin, int group_stride, int row_offset, int rows, const std::string& head,
-             int Cout, int P, int P_pad, float* out) {
+int run_head(const Ctx& c, const bf16* hin, int group_stride, int row_offset, int rows, const LinW& head, int Cout,
+             int P, int P_pad, float* out) {
   const pdm_uvit* h = c.h;
   pdm::HeadArgs a{};
   a.x = hin; a.ldx = h->D;
   a.in_group_stride = group_stride; a.in_row_offset = row_offset;
-  a.W = h->w(head + ".weight"); a.bias = h->f(head + ".bias");
+  a.W = head.w; a.bias = head.bias;
   a.out = out;
   a.B = rows; a.D = h->D; a.C = Cout; a.p = h->p; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size;
   a.P = P; a.P_pad = P_pad; a.act_tanh = 0;
@@ -829,23 +709,30 @@ int run_head(const Ctx& c, const bf16* hin, int group_stride, int row_offset, in
   return PDM_OK;
 }
 
-// final LayerNorm over the patch tokens of X (rows extras .. L-1 of each sequence) -> HEADIN, optionally
-// adding fp32 rows `add` (use_ground_truth: libs/uvit_t2i.py:486-494) after the affine
-int final_norm(const Ctx& c, const Workspace& w, int rows, const float* X, int L, const float* add = nullptr,
-               int add_gs = 0, int add_off = 0, const bf16* Xb = nullptr, const bf16* addb = nullptr) {
-  const pdm_uvit* h = c.h;
+// The final LayerNorm over rows [extras, extras + per_seq) of each L-row sequence of the result (XB on the bf16
+// stream, X on the fp32 one) -> HEADIN [rows][per_seq][D]; a caller adds what its tail sums into the norm
+pdm::LayerNormArgs final_norm(const pdm_uvit* h, const Workspace& w, int rows, int L, int per_seq) {
   pdm::LayerNormArgs a{};
-  a.x = Xb ? nullptr : X; a.xb = Xb; a.ldx = h->D;
-  a.addb = addb;
-  a.gamma = h->f("norm.weight"); a.beta = h->f("norm.bias");
+  if (h->res16()) a.xb = w.XB; else a.x = w.X;
+  a.ldx = h->D;
+  a.gamma = h->norm_w; a.beta = h->norm_b;
   a.y = w.HEADIN; a.ldy = h->D;
-  a.rows = rows * h->n_patch; a.D = h->D;
-  a.rows_per_group = h->n_patch; a.group_stride = L; a.row_offset = h->extras;
+  a.rows = rows * per_seq; a.D = h->D;
+  a.rows_per_group = per_seq; a.group_stride = L; a.row_offset = h->extras;
   a.eps = 1e-5f;
-  a.add = add; a.add_ld = h->D; a.add_group_stride = add_gs; a.add_row_offset = add_off;
-  PDM_CHECK(pdm::layernorm_check(a));
-  PDM_HIP(pdm::layernorm_launch(a, c.s));
-  return PDM_OK;
+  a.add_ld = h->D;
+  return a;
+}
+
+// The tail of every forward: the final norm, the mask head on rows (group stride mask_gs, offset mask_off) of
+// mask_in unless that is null, then the noise head on the first n_patch rows of each HEADIN group
+int run_tail(const Ctx& c, const Workspace& w, int rows, const pdm::LayerNormArgs& ln, const bf16* mask_in,
+             int mask_gs, int mask_off, float* eps_pre, float* mask_pre) {
+  const pdm_uvit* h = c.h;
+  PDM_CHECK(pdm::layernorm_check(ln));
+  PDM_HIP(pdm::layernorm_launch(ln, c.s));
+  if (mask_in) PDM_TRY(run_head(c, mask_in, mask_gs, mask_off, rows, h->head_mask, h->K, h->PK, h->PK_pad, mask_pre));
+  return run_head(c, w.HEADIN, ln.rows_per_group, 0, rows, h->head, h->C, h->P, h->P_pad, eps_pre);
 }
 
 // The panoptic two-stream U-ViT (libs/uvit_t2i.py:411-525) on the bf16 residual stream, after the image tokens
@@ -853,11 +740,14 @@ int final_norm(const Ctx& c, const Workspace& w, int rows, const float* X, int L
 // is rebuilt in MB (image rows copied from the image block's INPUT x, 426 / 443 / 459; mask rows from the
 // previous mask block's output), both blocks run, then x += zeroconv(mask block output[:, :Lx]) (435-436,
 // 452-453, 470-472) as a residual GEMM into the image output buffer.
-int t2i_two_stream16(const Ctx& c, const Workspace& w, int rows, int use_ground_truth, float* eps_pre,
+int t2i_two_stream16(const Ctx& c, Mode m, const Workspace& w, int rows, int use_ground_truth, float* eps_pre,
                      float* mask_pre) {
   const pdm_uvit* h = c.h;
-  const int D = h->D, Lx = h->Lx, Lm = h->Lm, n = h->nhalf, T = (D + 255) / 256;
+  const int D = h->D, Lx = h->Lx, Lm = h->Lm, T = (D + 255) / 256;
   const size_t MDx = (size_t)rows * Lx * D, MDm = (size_t)rows * Lm * D;
+  // the image block's own scratch: always present here, since layout() allocates it for every separate panoptic net
+  // on the bf16 stream without MXFP8, and pdm_uvit_create rejects MXFP8 t2i nets
+  if (!w.XT2) return fail(PDM_ERR_STATE, "t2i_two_stream16: no image-stream scratch in this workspace");
   // bf16 row copies of D columns (as fp32 words: D / 2 per row), optionally with the rows' LayerNorm partials
   auto copy_rows = [&](bf16* dst, const bf16* src, int rpg, int dgs, int sgs, float* st_dst = nullptr,
                        const float* st_src = nullptr) -> int {
@@ -865,85 +755,85 @@ int t2i_two_stream16(const Ctx& c, const Workspace& w, int rows, int use_ground_
                                 st_dst, 2 * T, st_src, 2 * T, 2 * T));
     return PDM_OK;
   };
-  // mb = cat(x_img, m_src[:, Lx:]) + its partials (m_src == MB: the mask rows are already in place).  The mask
-  // rows' LayerNorm partials are already in STM (written there by the mask block that produced m_src, in its fc2
-  // epilogue, or by the token assembly).  The image rows and their partials come from the injection GEMM's second
-  // output (img_in_place), and only before the first layer from x itself (XB / ST of the assembly).
-  auto refresh = [&](const bf16* x_img, const bf16* m_src, bool img_in_place) -> int {
-    if (!img_in_place) PDM_TRY(copy_rows(w.MB, x_img, Lx, Lm, Lx, w.STM, w.ST));
-    if (m_src != w.MB) PDM_TRY(copy_rows(w.MB + (size_t)Lx * D, m_src + (size_t)Lx * D, Lm - Lx, Lm, Lm));
-    return PDM_OK;
-  };
-  // x_out = x_res + zeroconv(mout[:, :Lx]), also stored (with its partials) as the image rows of MB -- the next
-  // layer's mask-stream input; mout (SKM[i] / MXB) is never MB, so no tile reads rows another one writes
-  auto inject = [&](int layer, const bf16* mout, const bf16* x_res, bf16* x_out) -> int {
-    const std::string zc = "zero_convs." + std::to_string(2 * layer + 1) + ".conv";
-    pdm::GemmArgs a{};
-    a.A1 = mout; a.lda1 = D; a.K1 = D;
-    a.a_rows_per_group = Lx; a.a_group_stride = Lm;
-    a.W = h->w(zc + ".weight"); a.bias = h->f(zc + ".bias");
-    a.M = rows * Lx; a.N = D; a.K = D;
-    a.out_bf16 = x_out; a.ldo = D;
-    a.res_in = x_res; a.ldri = D; a.accumulate = 1;
-    a.stats_out = w.ST; a.stats_ld = T;
-    a.out2 = w.MB; a.out2_rpg = Lx; a.out2_gs = Lm;
-    a.stats_out2 = w.STM;
-    return launch_gemm(c, a, pdm::EPI_RES);
-  };
-  // image tokens -> XB + ST; mask tokens -> MB[:, Lx:] (the image rows of this pass are overwritten by refresh)
+  // image tokens -> XB + ST; mask tokens -> MB[:, Lx:] (the image rows of this pass are overwritten by the refresh)
   PDM_TRY(row_stats(c, w.X, rows * Lx, w.XB, w.ST));
   PDM_TRY(row_stats(c, w.MX, rows * Lm, w.MB, w.STM));
   const bf16* x = w.XB;
-  const bf16* m = w.MB;
-  int layer = 0;
-  // Per layer the mask block runs first (its input only needs the image block's INPUT x), then the image block,
-  // whose output stays in XT (its proj / fc2 update XT in place), then the injection writes the layer's x.  The
-  // mask block's fc2 writes its output's partials into STM (the next refresh keeps the mask rows' ones); the
-  // image block's are not needed (the injection produces x's).
-  // the mask block and the image block of a layer: paired (one grouped launch per Linear) when the image stream has
-  // its own scratch (the image block's output then lives in XT2 instead of XT), else one after the other
-  const bool pair = w.XT2 != nullptr;
-  bf16* ximg = pair ? w.XT2 : w.XT;   // the image block's output (the injection's residual)
-  auto blocks = [&](const std::string& mpre, const std::string& ipre, const bf16* skm, const bf16* sk, const bf16* xin,
-                    bf16* mout) -> int {
-    if (pair) {
-      const BlockIO mio{mpre, Lm, w.MB, w.STM, skm, mout, w.STM, w.XT, w.QKV, w.ATT, w.MLP, w.STT};
-      // the image block's fc2 partials are not needed (the injection produces x's); they land in its scratch STT2
-      // so both fc2s take the same epilogue and group
-      const BlockIO iio{ipre, Lx, xin, w.ST, sk, w.XT2, w.STT2, w.XT2, w.QKV2, w.ATT2, w.MLP2, w.STT2};
-      return run_block16_pair(c, rows, mio, iio);
+  const bf16* mprev = w.MB;
+  for (const Layer& ly : h->layers) {
+    // refresh mb = cat(x, m) + its partials.  The image rows and their partials came from the previous layer's
+    // injection (its second output), and only before the first layer from x itself (XB / ST of the assembly).  The
+    // mask rows' partials are already in STM, written by the mask block that produced them (its fc2 epilogue) or by
+    // the token assembly; the rows themselves are copied unless already in place.
+    if (&ly == &h->layers.front()) PDM_TRY(copy_rows(w.MB, x, Lx, Lm, Lx, w.STM, w.ST));
+    if (mprev != w.MB) PDM_TRY(copy_rows(w.MB + (size_t)Lx * D, mprev + (size_t)Lx * D, Lm - Lx, Lm, Lm));
+    // the mask block and the image block in lockstep, every Linear of the pair one grouped launch.  The mask block
+    // only needs the image block's INPUT x; the image block's output stays in its scratch XT2 (proj / fc2 update it
+    // in place), and its fc2 partials, which nobody reads (the injection produces x's), land in STT2 so that both
+    // fc2s take the same epilogue and group.
+    bf16* mout = ly.keep >= 0 ? w.SKM + ly.keep * MDm : w.MXB;
+    bf16* xout = ly.keep >= 0 ? w.SK + ly.keep * MDx : w.XB;
+    BlockIO io[2] = {block_io(w, ly.mask, Lm), block_io(w, ly.img, Lx)};
+    io[0].xin = w.MB; io[0].st_in = w.STM; io[0].xout = mout; io[0].st_out = w.STM;
+    io[1].xin = x; io[1].st_in = w.ST; io[1].xout = w.XT2; io[1].st_out = w.STT2;
+    io[1].XT = w.XT2; io[1].QKV = w.QKV2; io[1].ATT = w.ATT2; io[1].MLP = w.MLP2; io[1].STT = w.STT2;
+    if (ly.skip_from >= 0) {
+      io[0].skip_in = w.SKM + ly.skip_from * MDm;
+      io[1].skip_in = w.SK + ly.skip_from * MDx;
     }
-    PDM_TRY(run_block16(c, mpre, rows, Lm, w.MB, w.STM, skm, mout, w.STM, w));
-    return run_block16(c, ipre, rows, Lx, xin, w.ST, sk, w.XT, nullptr, w);
-  };
-  for (int i = 0; i < n; ++i, ++layer) {
-    PDM_TRY(refresh(x, m, i > 0));
-    PDM_TRY(blocks("in_blocks_mask." + std::to_string(i), "in_blocks." + std::to_string(i), nullptr, nullptr, x,
-                   w.SKM + i * MDm));
-    PDM_TRY(inject(layer, w.SKM + i * MDm, ximg, w.SK + i * MDx));
-    x = w.SK + i * MDx;
-    m = w.SKM + i * MDm;
+    PDM_TRY(run_block(c, m, rows, 2, io, w));
+    // inject: x_out = x + zeroconv(mout[:, :Lx]), also stored (with its partials) as the image rows of MB -- the
+    // next layer's mask-stream input; mout (SKM[i] / MXB) is never MB, so no tile reads rows another one writes
+    pdm::GemmArgs a = res_lin(h, m, mout, D, nullptr, ly.zc, rows * Lx, D, nullptr, w.XT2, xout, w.ST);
+    a.a_rows_per_group = Lx; a.a_group_stride = Lm;
+    a.out2 = w.MB; a.out2_rpg = Lx; a.out2_gs = Lm;
+    a.stats_out2 = w.STM;
+    PDM_TRY(launch_gemm(c, a, pdm::EPI_RES));
+    x = xout;
+    mprev = mout;
   }
-  PDM_TRY(refresh(x, m, n > 0));
-  PDM_TRY(blocks("mid_block_mask", "mid_block", nullptr, nullptr, x, w.MXB));
-  PDM_TRY(inject(layer, w.MXB, ximg, w.XB));
-  ++layer;
-  for (int i = 0; i < n; ++i, ++layer) {
-    PDM_TRY(refresh(w.XB, w.MXB, true));
-    const bf16* skm = h->cfg.skip ? w.SKM + (n - 1 - i) * MDm : nullptr;
-    const bf16* sk = h->cfg.skip ? w.SK + (n - 1 - i) * MDx : nullptr;
-    PDM_TRY(blocks("out_blocks_mask." + std::to_string(i), "out_blocks." + std::to_string(i), skm, sk, w.XB, w.MXB));
-    PDM_TRY(inject(layer, w.MXB, ximg, w.XB));
+  // heads (477-519): noise from norm(x) patch tokens (+ the mask rows, use_ground_truth: 486-494); the mask head on
+  // the un-normalised m (the last mask output)
+  pdm::LayerNormArgs ln = final_norm(h, w, rows, Lx, h->n_patch);
+  if (use_ground_truth) { ln.addb = w.MXB; ln.add_group_stride = Lm; ln.add_row_offset = Lx; }
+  return run_tail(c, w, rows, ln, use_ground_truth ? nullptr : w.MXB, Lm, Lx, eps_pre, mask_pre);
+}
+
+// The same network on the fp32 residual stream: x in X, the mask stream mx = cat(x, m) in MX, one block after the
+// other.  Before every mask block the image half of MX is refreshed from X (426, 443, 459) and the whole mask
+// stream's bf16 copy + partials redone (its blocks' qkv / skip_linear operand); the injection adds into X and
+// leaves bf16 of the new x (the long skip / next block's operand) and its partials.
+int t2i_two_stream32(const Ctx& c, Mode m, const Workspace& w, int rows, int use_ground_truth, float* eps_pre,
+                     float* mask_pre) {
+  const pdm_uvit* h = c.h;
+  const int D = h->D, Lx = h->Lx, Lm = h->Lm;
+  const size_t MDx = (size_t)rows * Lx * D, MDm = (size_t)rows * Lm * D;
+  PDM_TRY(row_stats(c, w.X, rows * Lx, w.XB, w.ST));
+  const bf16* xb = w.XB;
+  for (const Layer& ly : h->layers) {
+    PDM_HIP(pdm::rowcopy_launch(w.MX, D, w.X, D, rows * Lx, D, Lx, Lm, Lx, c.s));
+    PDM_TRY(row_stats(c, w.MX, rows * Lm, w.MXIN, w.STM));
+    bf16* mout = ly.keep >= 0 ? w.SKM + ly.keep * MDm : w.MXB;
+    bf16* xout = ly.keep >= 0 ? w.SK + ly.keep * MDx : w.XB;
+    BlockIO si = block_io(w, ly.img, Lx), sm = block_io(w, ly.mask, Lm);
+    si.X = w.X; si.xin = xb; si.st_in = w.ST;
+    sm.X = w.MX; sm.xin = w.MXIN; sm.st_in = w.STM; sm.xout = mout;
+    if (ly.skip_from >= 0) {
+      si.skip_in = w.SK + ly.skip_from * MDx;
+      sm.skip_in = w.SKM + ly.skip_from * MDm;
+    }
+    PDM_TRY(run_block(c, m, rows, 1, &si, w));
+    PDM_TRY(run_block(c, m, rows, 1, &sm, w));
+    // inject: x += zeroconv(mx[:, :Lx]) from the bf16 copy of the mask block output
+    pdm::GemmArgs a = res_lin(h, m, mout, D, nullptr, ly.zc, rows * Lx, D, w.X, nullptr, xout, w.ST);
+    a.a_rows_per_group = Lx; a.a_group_stride = Lm;
+    PDM_TRY(launch_gemm(c, a, pdm::EPI_F32));
+    xb = xout;
   }
-  // heads (477-519): noise from norm(x) patch tokens; mask head on the un-normalised m (the last mask output)
-  if (use_ground_truth) {
-    PDM_TRY(final_norm(c, w, rows, nullptr, Lx, nullptr, Lm, Lx, w.XB, w.MXB));
-  } else {
-    PDM_TRY(final_norm(c, w, rows, nullptr, Lx, nullptr, 0, 0, w.XB));
-    PDM_TRY(run_head(c, w.MXB, Lm, Lx, rows, "decoder_pred_mask", h->K, h->PK, h->PK_pad, mask_pre));
-  }
-  PDM_TRY(run_head(c, w.HEADIN, h->n_patch, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre));
-  return PDM_OK;
+  // heads: as on the bf16 stream, with the un-normalised m = MX[:, Lx:] in fp32 and its bf16 copy MXB
+  pdm::LayerNormArgs ln = final_norm(h, w, rows, Lx, h->n_patch);
+  if (use_ground_truth) { ln.add = w.MX; ln.add_group_stride = Lm; ln.add_row_offset = Lx; }
+  return run_tail(c, w, rows, ln, use_ground_truth ? nullptr : w.MXB, Lm, Lx, eps_pre, mask_pre);
 }
 
 }  // namespace
@@ -1073,9 +963,7 @@ int pdm_uvit_create(const pdm_uvit_cfg* cfg, pdm_uvit** out) {
     h->add("context_embed.weight", PDM_BF16, (long long)D * c.clip_dim);
     h->add("context_embed.bias", PDM_F32, D);
   }
-  for (int i = 0; i < h->nhalf; ++i) h->add_block("in_blocks." + std::to_string(i), false);
-  h->add_block("mid_block", false);
-  for (int i = 0; i < h->nhalf; ++i) h->add_block("out_blocks." + std::to_string(i), c.skip != 0);
+  h->add_stack("");
   h->add("norm.weight", PDM_F32, D);
   h->add("norm.bias", PDM_F32, D);
   h->add("decoder_pred.weight", PDM_BF16, (long long)h->P_pad * D);
@@ -1086,13 +974,10 @@ int pdm_uvit_create(const pdm_uvit_cfg* cfg, pdm_uvit** out) {
     h->add("mask_embed.proj.bias", PDM_F32, D);
     h->add("decoder_pred_mask.weight", PDM_BF16, (long long)h->PK_pad * D);
     h->add("decoder_pred_mask.bias", PDM_F32, h->PK);
-    for (int i = 0; i < h->nhalf; ++i) h->add_block("in_blocks_mask." + std::to_string(i), false);
-    h->add_block("mid_block_mask", false);
-    for (int i = 0; i < h->nhalf; ++i) h->add_block("out_blocks_mask." + std::to_string(i), c.skip != 0);
+    h->add_stack("_mask");
     for (int i = 0; i <= c.depth; ++i) {
-      const std::string zc = "zero_convs." + std::to_string(2 * i + 1) + ".conv";
-      h->add(zc + ".weight", PDM_BF16, (long long)D * D);
-      h->add(zc + ".bias", PDM_F32, D);
+      h->add(pdm_uvit::zc_name(i) + ".weight", PDM_BF16, (long long)D * D);
+      h->add(pdm_uvit::zc_name(i) + ".bias", PDM_F32, D);
     }
   }
   if (h->joint()) {   // one stack: the mask patches' embedding and head only (mask_embed_0 is unused: 392-396)
@@ -1100,6 +985,14 @@ int pdm_uvit_create(const pdm_uvit_cfg* cfg, pdm_uvit** out) {
     h->add("mask_embed.proj.bias", PDM_F32, D);
     h->add("decoder_pred_mask.weight", PDM_BF16, (long long)h->PK_pad * D);
     h->add("decoder_pred_mask.bias", PDM_F32, h->PK);
+  }
+  const int n = h->nhalf;
+  h->layers.resize(2 * n + 1);
+  for (int l = 0; l <= 2 * n; ++l) {
+    Layer& ly = h->layers[l];
+    if (l < n) ly.keep = l;
+    if (l > n && c.skip) ly.skip_from = 2 * n - l;   // out-block i reads in-block n - 1 - i (libs/uvit.py:219-220)
+    ly.last = n > 0 && l == 2 * n;
   }
   *out = h;
   return PDM_OK;
@@ -1160,6 +1053,7 @@ int pdm_uvit_set_param(pdm_uvit* h, const char* name, const void* dev_ptr, int d
     return fail(PDM_ERR_ARG, std::string("pdm_uvit_set_param: dtype/size mismatch for ") + name);
   if (((uintptr_t)dev_ptr) & 15) return fail(PDM_ERR_ARG, std::string("pdm_uvit_set_param: 16-byte alignment required for ") + name);
   it->second.ptr = dev_ptr;
+  h->dirty = true;
   return PDM_OK;
 }
 
@@ -1180,39 +1074,12 @@ int pdm_uvit_forward(pdm_uvit* h, const float* x, const float* t, const int64_t*
   if (h->cfg.t2i) return fail(PDM_ERR_ARG, "pdm_uvit_forward: t2i network, use pdm_uvit_t2i_forward");
   if (h->cfg.num_classes > 0 && !y) return fail(PDM_ERR_ARG, "pdm_uvit_forward: labels required (num_classes > 0)");
   if (h->cfg.num_classes <= 0 && y) return fail(PDM_ERR_ARG, "pdm_uvit_forward: labels given to an unconditional net");
-  PDM_TRY(check_ready(h));
-  Workspace w = layout(h, rows, (char*)workspace);
-  if (w.bytes > workspace_bytes) return fail(PDM_ERR_ARG, "pdm_uvit_forward: workspace too small");
-  h->prof_n = 0;
-  Ctx c{h, (hipStream_t)stream};
-  int skn = 0;
-  PDM_TRY(sk_begin(c, &skn));
-  const int D = h->D, L = h->Lx;
-  {
-    pdm::AssembleArgs a{};
-    a.img = x; a.C = h->C; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
-    a.patch_w = h->f("patch_embed.proj.weight"); a.patch_b = h->f("patch_embed.proj.bias");
-    a.t = t; a.y = y;
-    a.label_emb = h->cfg.num_classes > 0 ? h->f("label_emb.weight") : nullptr;
-    a.pos = h->f("pos_embed");
-    a.out = w.X; a.ld_out = D;
-    a.B = rows; a.D = D; a.L_total = L;
-    a.row0_patch = h->extras;
-    a.time_row = h->extras - 1;
-    a.label_row = h->cfg.num_classes > 0 ? 0 : -1;   // token order [label, time, patches] (libs/uvit.py:205-211)
-    a.ctx_row = -1;
-    PDM_CHECK(pdm::assemble_check(a));
-    PDM_HIP(pdm::assemble_launch(a, c.s));
-  }
-  if (h->res16()) {
-    PDM_TRY(h->cfg.fp8 ? run_stack8_16(c, w, rows, L) : run_stack16(c, w, rows, L));
-    PDM_TRY(final_norm(c, w, rows, nullptr, L, nullptr, 0, 0, w.XB));
-  } else {
-    PDM_TRY(h->cfg.fp8 ? run_stack8(c, w, rows, L) : run_stack(c, w, rows, L));
-    PDM_TRY(final_norm(c, w, rows, w.X, L));
-  }
-  PDM_TRY(run_head(c, w.HEADIN, h->n_patch, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre));
-  return PDM_OK;
+  Workspace w;
+  Ctx c;
+  PDM_TRY(begin_forward(h, "pdm_uvit_forward", rows, workspace, workspace_bytes, stream, w, c));
+  PDM_TRY(assemble_image(c, w, x, t, y, rows, h->Lx));
+  PDM_TRY(run_stack(c, mode_of(h), w, rows, h->Lx));
+  return run_tail(c, w, rows, final_norm(h, w, rows, h->Lx, h->n_patch), nullptr, 0, 0, eps_pre, nullptr);
 }
 
 int pdm_uvit_t2i_forward(pdm_uvit* h, const float* x, const float* t, const float* context, const float* mask_token,
@@ -1222,142 +1089,43 @@ int pdm_uvit_t2i_forward(pdm_uvit* h, const float* x, const float* t, const floa
   if (!h->cfg.t2i) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: not a t2i network");
   if (mask_token && !h->cfg.enable_panoptic)
     return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: mask tokens need a network built with enable_panoptic");
-  const bool two = mask_token && h->cfg.separate;     // two block stacks with zero-conv injections
-  const bool joint = mask_token && !h->cfg.separate;  // one stack over [time, context, image patches, mask patches]
   if (mask_token && !use_ground_truth && !mask_pre)
     return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: mask tokens without use_ground_truth need the mask_pre output");
-  PDM_TRY(check_ready(h));
-  Workspace w = layout(h, rows, (char*)workspace);
-  if (w.bytes > workspace_bytes) return fail(PDM_ERR_ARG, "pdm_uvit_t2i_forward: workspace too small");
-  h->prof_n = 0;
-  Ctx c{h, (hipStream_t)stream};
-  int skn = 0;
-  PDM_TRY(sk_begin(c, &skn));
-  const int D = h->D, Lx = h->Lx, Lm = h->Lm, nctx = h->cfg.num_clip_token;
-  // context_embed (libs/uvit_t2i.py:387): bf16 cast + GEMM (+bias) -> fp32 context tokens
-  PDM_HIP(pdm::cast_bf16_launch(context, w.CTXB, (long long)rows * nctx * h->cfg.clip_dim, c.s));
-  PDM_TRY(gemm(c, w.CTXB, h->cfg.clip_dim, h->w("context_embed.weight"), h->f("context_embed.bias"), rows * nctx, D,
-               h->cfg.clip_dim, pdm::EPI_F32, nullptr, 0, w.CTXF, D, 0));
-  {  // image stream tokens [time, context x nctx, patches] + pos_embed (401-405 / 408-409)
-    pdm::AssembleArgs a{};
-    a.img = x; a.C = h->C; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
-    a.patch_w = h->f("patch_embed.proj.weight"); a.patch_b = h->f("patch_embed.proj.bias");
-    a.t = t; a.ctx_tokens = w.CTXF; a.n_ctx = nctx;
-    a.pos = h->f("pos_embed");
-    // (joint: the first Lx rows of each Lm-row sequence; either way only pos_embed rows [0, Lx) are read)
-    a.out = w.X; a.ld_out = D; a.B = rows; a.D = D; a.L_total = joint ? Lm : Lx;
-    a.row0_patch = h->extras; a.time_row = 0; a.label_row = -1; a.ctx_row = 1;
-    PDM_CHECK(pdm::assemble_check(a));
-    PDM_HIP(pdm::assemble_launch(a, c.s));
+  const bool joint = mask_token && !h->cfg.separate;  // one stack over [time, context, image patches, mask patches]
+  Workspace w;
+  Ctx c;
+  PDM_TRY(begin_forward(h, "pdm_uvit_t2i_forward", rows, workspace, workspace_bytes, stream, w, c));
+  const Mode m = mode_of(h);
+  const int D = h->D, Lx = h->Lx, Lm = h->Lm, N = h->n_patch, nctx = h->cfg.num_clip_token, cd = h->cfg.clip_dim;
+  {  // context_embed (libs/uvit_t2i.py:387): bf16 cast + GEMM (+bias) -> fp32 context tokens
+    PDM_HIP(pdm::cast_bf16_launch(context, w.CTXB, (long long)rows * nctx * cd, c.s));
+    pdm::GemmArgs a{};
+    a.A1 = w.CTXB; a.lda1 = cd; a.K1 = cd;
+    a.W = h->ctx_embed.w; a.bias = h->ctx_embed.bias;
+    a.M = rows * nctx; a.N = D; a.K = cd;
+    a.out_f32 = w.CTXF; a.ldr = D;
+    a.stats_ld = a.ln_ld = (D + 255) / 256; a.ln_D = cd; a.ln_eps = 1e-5f;   // (carried, unused: no LayerNorm here)
+    PDM_TRY(launch_gemm(c, a, pdm::EPI_F32));
   }
-  const size_t MDx = (size_t)rows * Lx * D;
-  if (joint) {  // separate=False (397-399, 419-520): the single stack over all Lm rows, both heads on norm(x)
-    const int N = h->n_patch;
-    {  // mask patches mask_embed(mask_token) + pos_embed[Lx:Lm] -> rows [Lx, Lm) of each sequence
-      pdm::AssembleArgs a{};
-      a.img = mask_token; a.C = h->K; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
-      a.patch_w = h->f("mask_embed.proj.weight"); a.patch_b = h->f("mask_embed.proj.bias");
-      a.pos = h->f("pos_embed") + (size_t)Lx * D;
-      a.out = w.X + (size_t)Lx * D; a.ld_out = D; a.B = rows; a.D = D; a.L_total = Lm;
-      a.row0_patch = 0; a.time_row = -1; a.label_row = -1; a.ctx_row = -1;
-      PDM_CHECK(pdm::assemble_check(a));
-      PDM_HIP(pdm::assemble_launch(a, c.s));
-    }
-    if (h->res16()) PDM_TRY(run_stack16(c, w, rows, Lm));
-    else PDM_TRY(run_stack(c, w, rows, Lm));
-    // final norm over the 2N patch rows only (rows [extras, Lm) of each sequence) -> HEADIN [rows][2N][D]; with
-    // use_ground_truth the image row and its mask row are normalised and summed in one pass -> HEADIN [rows][N][D]
-    pdm::LayerNormArgs a{};
-    if (h->res16()) a.xb = w.XB; else a.x = w.X;
-    a.ldx = D;
-    a.gamma = h->f("norm.weight"); a.beta = h->f("norm.bias");
-    a.y = w.HEADIN; a.ldy = D; a.D = D;
-    a.group_stride = Lm; a.row_offset = h->extras;
-    a.eps = 1e-5f;
-    if (use_ground_truth) {
-      a.rows = rows * N; a.rows_per_group = N; a.pair_offset = N;
-    } else {
-      a.rows = rows * 2 * N; a.rows_per_group = 2 * N;
-    }
-    PDM_CHECK(pdm::layernorm_check(a));
-    PDM_HIP(pdm::layernorm_launch(a, c.s));
-    if (use_ground_truth)
-      return run_head(c, w.HEADIN, N, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre);
-    PDM_TRY(run_head(c, w.HEADIN, 2 * N, N, rows, "decoder_pred_mask", h->K, h->PK, h->PK_pad, mask_pre));
-    return run_head(c, w.HEADIN, 2 * N, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre);
+  PDM_TRY(assemble_image(c, w, x, t, nullptr, rows, joint ? Lm : Lx));
+  if (mask_token && h->cfg.separate) {  // two block stacks with zero-conv injections
+    // mask tokens m = mask_embed(mask_token) + pos_embed_mask (390, 406), stored at MX[:, Lx:Lm]
+    PDM_TRY(assemble_mask(c, mask_token, h->pos_mask, w.MX, rows));
+    return (m.r16 ? t2i_two_stream16 : t2i_two_stream32)(c, m, w, rows, use_ground_truth, eps_pre, mask_pre);
   }
-  if (!two) {  // plain text-conditioned U-ViT (mask_token None: 407-410, 516-517)
-    if (h->res16()) {
-      PDM_TRY(run_stack16(c, w, rows, Lx));
-      PDM_TRY(final_norm(c, w, rows, nullptr, Lx, nullptr, 0, 0, w.XB));
-    } else {
-      PDM_TRY(run_stack(c, w, rows, Lx));
-      PDM_TRY(final_norm(c, w, rows, w.X, Lx));
-    }
-    PDM_TRY(run_head(c, w.HEADIN, h->n_patch, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre));
-    return PDM_OK;
+  if (!joint) {  // plain text-conditioned U-ViT (mask_token None: 407-410, 516-517)
+    PDM_TRY(run_stack(c, m, w, rows, Lx));
+    return run_tail(c, w, rows, final_norm(h, w, rows, Lx, N), nullptr, 0, 0, eps_pre, nullptr);
   }
-  {  // mask tokens m = mask_embed(mask_token) + pos_embed_mask (390, 406), stored at MX[:, Lx:Lm]
-    pdm::AssembleArgs a{};
-    a.img = mask_token; a.C = h->K; a.Himg = h->cfg.img_size; a.Wimg = h->cfg.img_size; a.p = h->p;
-    a.patch_w = h->f("mask_embed.proj.weight"); a.patch_b = h->f("mask_embed.proj.bias");
-    a.pos = h->f("pos_embed_mask");
-    a.out = w.MX + (size_t)Lx * D; a.ld_out = D; a.B = rows; a.D = D; a.L_total = Lm;
-    a.row0_patch = 0; a.time_row = -1; a.label_row = -1; a.ctx_row = -1;
-    PDM_CHECK(pdm::assemble_check(a));
-    PDM_HIP(pdm::assemble_launch(a, c.s));
-  }
-  const size_t MDm = (size_t)rows * Lm * D;
-  if (h->res16()) return t2i_two_stream16(c, w, rows, use_ground_truth, eps_pre, mask_pre);
-  // mx = cat(x, m): refresh the image half of the mask stream before every mask block (426, 443, 459), then
-  // the bf16 copy + LayerNorm partials of the whole mask stream (its blocks' qkv / skip_linear operand)
-  auto refresh = [&]() -> int {
-    PDM_HIP(pdm::rowcopy_launch(w.MX, D, w.X, D, rows * Lx, D, Lx, Lm, Lx, c.s));
-    return row_stats(c, w.MX, rows * Lm, w.MXIN, w.STM);
-  };
-  // x += zeroconv_{2l+1}(mx[:, :Lx]) (435-436, 452-453, 470-472) from the bf16 copy of the mask block output;
-  // the epilogue also leaves bf16 of the new x (the skip / next block's operand) in xb and its partials in ST
-  auto inject = [&](int layer, const bf16* mxb, bf16* xb) -> int {
-    const std::string zc = "zero_convs." + std::to_string(2 * layer + 1) + ".conv";
-    LnIO io;
-    io.st_out = w.ST;
-    return gemm(c, mxb, D, h->w(zc + ".weight"), h->f(zc + ".bias"), rows * Lx, D, D, pdm::EPI_F32, xb, D, w.X, D, 1,
-                nullptr, 0, 0, Lx, Lm, io);
-  };
-  PDM_TRY(row_stats(c, w.X, rows * Lx, w.XB, w.ST));
-  const bf16* xb = w.XB;
-  int layer = 0;
-  for (int i = 0; i < h->nhalf; ++i, ++layer) {
-    PDM_TRY(refresh());
-    PDM_TRY(run_block(c, "in_blocks." + std::to_string(i), w.X, rows, Lx, xb, w.ST, nullptr, nullptr, nullptr, w));
-    PDM_TRY(run_block(c, "in_blocks_mask." + std::to_string(i), w.MX, rows, Lm, w.MXIN, w.STM, nullptr,
-                      w.SKM + i * MDm, nullptr, w));
-    PDM_TRY(inject(layer, w.SKM + i * MDm, w.SK + i * MDx));
-    xb = w.SK + i * MDx;
-  }
-  PDM_TRY(refresh());
-  PDM_TRY(run_block(c, "mid_block", w.X, rows, Lx, xb, w.ST, nullptr, nullptr, nullptr, w));
-  PDM_TRY(run_block(c, "mid_block_mask", w.MX, rows, Lm, w.MXIN, w.STM, nullptr, w.MXB, nullptr, w));
-  PDM_TRY(inject(layer, w.MXB, w.XB));
-  ++layer;
-  for (int i = 0; i < h->nhalf; ++i, ++layer) {
-    PDM_TRY(refresh());
-    const bf16* sk = h->cfg.skip ? w.SK + (h->nhalf - 1 - i) * MDx : nullptr;
-    PDM_TRY(run_block(c, "out_blocks." + std::to_string(i), w.X, rows, Lx, w.XB, w.ST, sk, nullptr, nullptr, w));
-    const bf16* skm = h->cfg.skip ? w.SKM + (h->nhalf - 1 - i) * MDm : nullptr;
-    PDM_TRY(run_block(c, "out_blocks_mask." + std::to_string(i), w.MX, rows, Lm, w.MXIN, w.STM, skm, w.MXB, nullptr, w));
-    PDM_TRY(inject(layer, w.MXB, w.XB));
-  }
-  // heads (477-519): noise from norm(x) patch tokens; mask head on the un-normalised m (= MX[:, Lx:])
-  if (use_ground_truth) {
-    PDM_TRY(final_norm(c, w, rows, w.X, Lx, w.MX, Lm, Lx));
-  } else {
-    PDM_TRY(final_norm(c, w, rows, w.X, Lx));
-    const bf16* mb = h->nhalf > 0 ? w.MXB : w.MXB;  // bf16 copy of the last mask block output
-    PDM_TRY(run_head(c, mb, Lm, Lx, rows, "decoder_pred_mask", h->K, h->PK, h->PK_pad, mask_pre));
-  }
-  PDM_TRY(run_head(c, w.HEADIN, h->n_patch, 0, rows, "decoder_pred", h->C, h->P, h->P_pad, eps_pre));
-  return PDM_OK;
+  // separate=False (397-399, 419-520): mask patches + pos_embed[Lx:Lm] -> rows [Lx, Lm) of X, the single stack over
+  // all Lm rows, both heads on norm(x) of the 2N patch rows -> HEADIN [rows][2N][D]; with use_ground_truth the
+  // image row and its mask row are normalised and summed in one pass -> HEADIN [rows][N][D]
+  PDM_TRY(assemble_mask(c, mask_token, h->pos + (size_t)Lx * D, w.X, rows));
+  PDM_TRY(run_stack(c, m, w, rows, Lm));
+  pdm::LayerNormArgs ln = final_norm(h, w, rows, Lm, use_ground_truth ? N : 2 * N);
+  if (use_ground_truth) ln.pair_offset = N;
+  ln.add_ld = 0;   // (no added rows in this tail; it has always carried 0 here)
+  return run_tail(c, w, rows, ln, use_ground_truth ? nullptr : w.HEADIN, 2 * N, N, eps_pre, mask_pre);
 }
 
 int pdm_stage_epilogue(const pdm_stage_epilogue_args* a, void* stream) {

@@ -71,7 +71,7 @@ def test_full_t2i_forward_with_mask_vs_oracle(dev, coco):
 
 def test_full_t2i_forward_grouped_rows_vs_oracle(dev, coco):
     """At >= 13 rows every image- / mask-stream Linear pair of a layer is ONE grouped persistent launch (capi.hip
-    run_block16_pair -> pdm::gemm_launch_pair: both problems >= 4096 rows); the B <= 3 tests above take its two-launch
+    run_block on two streams -> pdm::gemm_launch_pair: both problems >= 4096 rows); the B <= 3 tests above take its two-launch
     fallback.  The grouped forward at B = 14 against the fp32 oracle (2e-2, as above) and against the same forward
     with grouping off (pdm_set_gemm_algo(7): separate whole-tile launches) to bf16 rounding (1e-2)."""
     torch.set_num_threads(min(16, torch.get_num_threads()))

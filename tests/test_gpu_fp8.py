@@ -89,7 +89,7 @@ def test_mx_output_epilogue_bit_exact(lib, algo, epi, M, N, K):
 @pytest.mark.parametrize("M,N,K", [(5160, 4608, 1152), (300, 4608, 256), (4133, 1184, 512)])
 def test_mx_only_output_bit_exact(lib, algo, epi, ln, M, N, K):
     """bf16-operand GEMM whose only output is the MXFP8 copy (the H/4 bf16 fc1 emitting the fc2 operand, capi.hip
-    run_block8): on the persistent kernel (algo 11, the default at these shapes) the fp8 bytes and E8M0 scales
+    run_block): on the persistent kernel (algo 11, the default at these shapes) the fp8 bytes and E8M0 scales
     are computed from registers (permlane reductions over the 4 lane rows of a 32-column block); they must equal
     the host quantiser applied to the bf16 output of the same algo with the same epilogue (LayerNorm consumer +
     GELU included), bit for bit -- and rows / columns past the tile edges stay untouched."""

@@ -606,10 +606,10 @@ def test_lincomb(lib):
                                   "mixed_n"])
 def test_gemm_pair_grouped_vs_separate(lib, case):
     """pdm_gemm_pair (one grouped persistent launch over the t2i image- and mask-stream Linears of a layer, csrc
-    capi.hip run_block16_pair) against the same two GEMMs launched alone: bit-identical outputs and partials (each
+    capi.hip run_block on two streams) against the same two GEMMs launched alone: bit-identical outputs and partials (each
     tile runs the same arithmetic in either launch).  Rows of the two problems as at the t2i bench (32 rows x 334 /
     590 tokens), D = 512; 'mixed_n' cannot be grouped (different N) and takes the two-launch path.  The residual
-    cases accumulate res_in (as the forward's res_args); 'fc2_res_inplace' reads the residual from the output
+    cases accumulate res_in (as the forward's res_lin); 'fc2_res_inplace' reads the residual from the output
     itself (res_in == out, the image block's fc2 adding into XT2)."""
     D, Hd = 512, 2048
     Ma, Mb = 32 * 334, 32 * 590

@@ -1,13 +1,13 @@
 #!/usr/bin/env python3
 """CPU ablation of the MXFP8 forward error (BASELINE configs[4], U-ViT-H/4): the fp32 oracle forward
 (oracle/uvit_ref.py, libs/uvit.py:115-120) with the block Linears fake-quantised exactly as the HIP fp8 path
-computes them (csrc/capi.hip run_block8):
+computes them (csrc/capi.hip run_block):
 
   qkv, fc1   operand MX(x) of the RAW residual row (optionally centred per 256-column group, --center), weight
              MX(W * gamma), LayerNorm applied to the accumulator: rstd * (acc - mean * colsum) + (W beta + b)
   proj       MX(bf16(attention output)) x MX(W)
   fc2        MX(bf16(GELU(fc1))) x MX(W)
-  skip_linear stays bf16 in the product (run_block8); it can be quantised here for the record (--skip8)
+  skip_linear stays bf16 in the product (run_block); it can be quantised here for the record (--skip8)
 
 Prints the forward rel-L2 vs the unquantised oracle for: all four in MXFP8, each one alone in MXFP8, and
 each one kept in bf16 with the other three in MXFP8.  Test infrastructure only (imports oracle/).
